@@ -13,9 +13,13 @@ Multi-GPU: one process per GPU (torch.distributed.run); frames are sharded
 is built on rank 0 and sent with ONE RCCL broadcast; no other collective on
 the data path.  Timing: barrier + device sync on both sides, max over ranks.
 
-Extra JSON fields: roofline of the dominant kernel (mmse_solve) measured with
-HIP events on the launch stream, the MFMA apply kernel, the LS/HBM path
-(config 2), and a CPU baseline (the oracle's fp64 OpenMP port, rank 0 only).
+A plain run sets up, warms up, times the --steps steps, writes the last
+step's H under --dump-outputs DIR when asked, and prints the result line.
+With --full it goes on to the extra JSON fields: roofline of the dominant
+kernel (mmse_solve) measured with HIP events on the launch stream, the MFMA
+apply kernel, the LS/HBM path (config 2), the other modes, sizes and
+configurations, and a CPU baseline (the oracle's fp64 OpenMP port, rank 0
+only); the full record goes to --extras-out.
 """
 import argparse
 import json
@@ -63,8 +67,14 @@ def parse():
     ap.add_argument("--mode", choices=["textbook", "ref"], default="textbook")
     ap.add_argument("--ls-frames", type=int, default=1 << 20, help="config-2 LS batch (past the 256 MiB MALL)")
     ap.add_argument("--c5-frames", type=int, default=131072, help="config-5 frames per GPU (1,048,576 / 8)")
-    ap.add_argument("--no-extras", action="store_true", help="headline only (for profiling runs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every extra leg (rooflines, other modes and sizes, host "
+                         "pipeline, CPU baselines) and write --extras-out; off: set up, warm up, time the steps, "
+                         "print the line")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra GPU legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's H, PS_MMSE) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU work budget of the baseline sample")
     ap.add_argument("--extras-out", default=os.path.join("gpurun_out", "bench_extras.json"),
                     help="full per-leg JSON (the stdout line carries one-number summaries)")
@@ -364,6 +374,26 @@ def power_clock(stream, step, seconds=2.5):
             "note": "amd-smi metric during back-to-back headline launches (untimed); the spec peak assumes 2,400 MHz"}
 
 
+DUMP_LIMIT = 64_000_000   # bytes of .npy payload per --dump-outputs run
+
+
+def dump_outputs(path, H, B):
+    """--dump-outputs: the H (PS_MMSE, complex fp64) the last timed step left
+    in HBM, as float64 [..., (re, im)] in DIR/ps_mmse.npy.  A batch over the
+    limit is sampled: a fixed seeded set of frames, ascending, whose indices
+    go to DIR/ps_mmse_frames.npy.  The inputs are the seeded synthetic frames,
+    so equal arguments give equal files from build to build."""
+    os.makedirs(path, exist_ok=True)
+    fit = (DUMP_LIMIT - 4096) // (N * 16 + 8)
+    if B <= fit:
+        h = H.numpy()
+    else:
+        pick = np.sort(np.random.default_rng(0x80211).choice(B, size=fit, replace=False))
+        h = np.concatenate([H.rows(i) for i in pick])
+        np.save(os.path.join(path, "ps_mmse_frames.npy"), pick.astype(np.float64))
+    np.save(os.path.join(path, "ps_mmse.npy"), np.ascontiguousarray(h).view(np.float64).reshape(h.shape + (2,)))
+
+
 def time_events(wce, stream, fn, reps):
     e0, e1 = wce.Event(), wce.Event()
     e0.record(stream)
@@ -378,6 +408,9 @@ def main():
     rc = check_world(args.gpus)
     if rc is not None:
         sys.exit(rc)
+    # a plain run is the headline alone; --full adds the extra legs
+    extras = args.full and not args.no_extras
+    cpu_legs = args.full and not args.no_cpu_baseline
     dist = Dist()
     if args.dry_run:
         return dry_run(args, dist)
@@ -440,6 +473,8 @@ def main():
     # max over ranks is an 8-byte all-reduce outside the timed region
     _, bad = ctx.nonfinite_scan(H, B, stream=s)
     nonfinite = int(dist.max(float(bad)))
+    if args.dump_outputs and dist.rank == 0:
+        dump_outputs(args.dump_outputs, H, B)    # before any extra leg reuses H
     total_frames = B * dist.world * args.steps
     value = total_frames / elapsed
     res = {"metric": METRIC, "value": value, "unit": "frames/s", "n_gpus": dist.world, "steps": args.steps,
@@ -455,7 +490,7 @@ def main():
                       "frames_per_gpu": B, "global_frames": B * dist.world, "subcarriers": N, "ofdm_blocks": NBLK,
                       "parallelism": f"dp{dist.world} (frames sharded, 1 RCCL state broadcast)"}}
 
-    if not args.no_extras:
+    if extras:
         # Dominant kernel = the whole step: for the rank-1 covariances (TEXTBOOK,
         # REF) one launch of mmse_solve_fc_kernel does the MMSE (Cholesky with two
         # bordered rows, H = u s).  HIP events on the launch stream.  The kernel
@@ -490,7 +525,7 @@ def main():
             if pc:
                 res["roofline"]["board"] = pc
 
-    if not args.no_extras and dist.rank == 0:
+    if extras and dist.rank == 0:
         try:
             # the general path: dense C (WCE_MMSE_COV, full-rank model Rhh): solve with
             # back-substitution, then H = C W on the f64 MFMA (apply_kernel).
@@ -593,7 +628,7 @@ def main():
         except Exception as e:  # noqa: BLE001 -- recorded in the leg's slot
             res.setdefault("cov_mode", {})["error"] = f"{type(e).__name__}: {e}"[:240]
 
-    if not args.no_extras:
+    if extras:
         reps = max(5, args.steps)
         # the other MMSE mode, same kernels
         other = wce.MMSE_REF if mode == wce.MMSE_TEXTBOOK else wce.MMSE_TEXTBOOK
@@ -645,7 +680,7 @@ def main():
                                                        prewarm_s=args.prewarm_s)
 
 
-    if not args.no_cpu_baseline and dist.rank == 0 and dist.world == 1:
+    if cpu_legs and dist.rank == 0 and dist.world == 1:
         guarded(res, "cpu_baseline", lambda: cpu_baseline(wce, ctx, frames, tx, rx, B, mode, args.cpu_seconds))
         if "error" not in res["cpu_baseline"]:
             refc = guarded({}, "r", lambda: cpu_reference(args.cpu_seconds / 2))
@@ -654,7 +689,7 @@ def main():
 
     res["dist_check"] = dist.group_check()
     if dist.rank == 0:
-        emit(res, args.extras_out)
+        emit(res, args.extras_out if args.full else None)
     dist.close()
 
 

@@ -5,8 +5,9 @@ set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 RND=${1:-r02}
 G=$R/gpurun_out
-cp "$G/bench_full.json" "$R/profiles/${RND}_bench.json"
-cp "$G/stats/run_kernel_stats.csv" "$R/profiles/${RND}_kernel_stats.csv"
+B=${WCE_OUT:-$R/bench_out}    # the full bench line and its profile (tools/refresh_profiles.sh's $O)
+cp "$B/bench_full.json" "$R/profiles/${RND}_bench.json"
+cp "$B/stats/run_kernel_stats.csv" "$R/profiles/${RND}_kernel_stats.csv"
 [ -f "$G/stats_head/run_kernel_stats.csv" ] && cp "$G/stats_head/run_kernel_stats.csv" "$R/profiles/${RND}_kernel_stats_headline.csv"
 [ -f "$G/pmc_legs.json" ] && cp "$G/pmc_legs.json" "$R/profiles/${RND}_pmc_legs.json"
 echo "collected into profiles/ as ${RND}_*"

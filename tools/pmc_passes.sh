@@ -8,8 +8,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/${PMC_DIR:-pmc}
 mkdir -p "$OUT"
 # PMC_EXTRAS=1: profile every bench leg (LS, front end, config 5, ...), not just the headline
-EXTRAS=--no-extras
-[ -n "$PMC_EXTRAS" ] && EXTRAS=
+EXTRAS=
+[ -n "$PMC_EXTRAS" ] && EXTRAS=--full
 rocprofv3 -L > "$OUT/counters_list.txt" 2>&1 || true
 run() {
   local name=$1; shift
