@@ -634,7 +634,13 @@ static int estimate_impl(wce_ctx *c, const wce_frames *in, const wce_outputs *ou
     // 1..8 (the lane kernels are already bound by the frames' HBM traffic).
     const bool cm = mmse && c->mode == WCE_MMSE_COV && c->cm_on && c->cm_use && in->semantics == WCE_SEM_C &&
                     !(mask & WCE_MMSE_FRAME_COV) && (lr_k0 < 0 || c->cov_rank > wce::LRL_RMAX);
-    const bool fuse = c->fuse && ls && mmse && in->semantics == WCE_SEM_C && lr_k0 < 0 && !cm;
+    // A rank-1 covariance (TEXTBOOK's shared C, or any per-frame C off REF's pilot form) is solved in closed
+    // form by a kernel bound by the frames' HBM traffic (mmse_rank1_kernel): no VALU-bound solve is left
+    // for the LS traffic to hide under, so such a request runs the LS pass, then that kernel.
+    const bool ref_dot = c->mode == WCE_MMSE_REF && c->bdot;
+    const bool closed = wce::variant_value(wce::WCE_VARIANT_R1) != 1 &&
+                        ((mask & WCE_MMSE_FRAME_COV) ? !ref_dot : (c->mode == WCE_MMSE_TEXTBOOK && c->bdot));
+    const bool fuse = c->fuse && ls && mmse && in->semantics == WCE_SEM_C && lr_k0 < 0 && !cm && !closed;
     const wce::LsArgs la = ls_args(in, out, mask, eq_src);
     if (ls && !fuse) {
         rc = wce::launch_ls(c->d_state, la, stream);

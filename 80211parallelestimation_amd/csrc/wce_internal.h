@@ -203,6 +203,8 @@ struct FrontArgs {
 int launch_ls(const State *st, const LsArgs &a, void *stream);
 int launch_front(const FrontArgs &a, bool preamble, void *stream);
 int launch_mmse_solve(const State *st, const SolveArgs &a, void *stream);
+// the closed-form rank-1 solve (wce_rank1.hip): every hout && !ref_pilots request of launch_mmse_solve
+int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, void *stream);
 // solve + LS family + equalization of each frame in one launch (C semantics, one block)
 int launch_mmse_solve_ls(const State *st, const SolveArgs &a, const LsArgs &l, void *stream);
 int launch_mmse_apply(const State *st, const double *W, double *H, int64_t stride, int64_t n, void *stream,
@@ -264,7 +266,14 @@ constexpr int WCE_VARIANT_REF_FC = 4;  // WCE_MMSE_FRAME_COV, C semantics: 0 = r
                                       // u / w products and the read-out in one launch; TEXTBOOK: LT_LS and
                                       // u = Mu h in one launch; default), 1 = the LT_LS pass + the matvec
                                       // launches (+ the REF read-out); bit-identical
-constexpr int WCE_VARIANT_COUNT = 5;
+constexpr int WCE_VARIANT_R1 = 5;      // PS_MMSE with a rank-1 covariance (TEXTBOOK, WCE_MMSE_FRAME_COV): 0 = the
+                                      // closed form (mmse_rank1_kernel, 16 lanes per unit, default; a request
+                                      // that also asks for LS outputs runs the LS pass, then this kernel),
+                                      // 1 = the 53 x 53 factorisation (mmse_solve_fc_kernel, one wave per unit,
+                                      // and the fused mmse_solve_ls_kernel), 2 = the closed form with
+                                      // nontemporal loads and stores; 0 and 2 bit-identical, 0 and 1 agree to
+                                      // ~1e-11 (each within 1e-10 of the long double answer)
+constexpr int WCE_VARIANT_COUNT = 6;
 int variant_value(int which);
 int set_variant(int which, int value);
 int launch_ldc_convert(const void *src, void *dst, int64_t n, bool to_complex, void *stream);

@@ -14,11 +14,13 @@
 //                         for free), LDS for the pivot-column broadcast
 //                         (main.c:148-212 / WiFi_channel_estimation_PS_MMSE.m).
 //                         Two read-outs:
-//   mmse_solve_fc_kernel    rank-1 C = u w^T (TEXTBOOK, per-frame C; the
-//                           headline): Cholesky with row-per-lane panels (one
-//                           full-wave publish per pivot, dot_factor); a second
-//                           bordered row (w o x)^T leaves s = w^T X z in the
-//                           Schur complement; H = u s, one launch.
+//   mmse_solve_fc_kernel    rank-1 C = u w^T by factorisation: Cholesky with
+//                           row-per-lane panels (dot_factor); a second bordered
+//                           row (w o x)^T leaves s = w^T X z in the Schur
+//                           complement; H = u s.  Since the closed form
+//                           (mmse_rank1_kernel, wce_rank1.hip: the headline,
+//                           TEXTBOOK and per-frame C) it runs REF's split
+//                           per-frame C and as the A/B variant WCE_VARIANT_R1 = 1.
 //   mmse_solve_kernel       dense C (COV): row-per-lane Cholesky keeping L,
 //                           blocked back-substitution, W = X z;
 //   apply_kernel            then H = C W on v_mfma_f64_16x16x4_f64 + 4x4x4_4b
@@ -29,7 +31,9 @@
 //                         (main.c:37-53 + 148-212), one persistent launch.
 //   cm_real_kernel        constant-modulus operator H = K (conj(x) o rx).
 //   mmse_solve_ls_kernel  config 5: either solve with the LS family and
-//                         equalization of the same frame in its epilogue.
+//                         equalization of the same frame in its epilogue
+//                         (dense C; a rank-1 C runs the LS pass, then
+//                         mmse_rank1_kernel).
 //   fc_finish_kernel      MATLAB averaging of the per-block s values.
 //   synth_kernel          counter-RNG synthetic frames (bench / tests).
 // The time-domain front end is in wce_front.hip.
@@ -3007,7 +3011,7 @@ constexpr int64_t LR_FPW_BELOW = 131072;
 // 5 63.1 -> 40.8, 6 65.8 -> 46.8, 7 75.4 -> 53.0, 8 68.1 -> 64.4 (before the LDS sharing: rank 4 direct 51.6 vs
 // staged ~60 at 65,536, so 98,304 then)
 constexpr int64_t LR_STAGE_FROM = 0;
-static int g_variant[WCE_VARIANT_COUNT] = {0, 2, 0, 0, 0};
+static int g_variant[WCE_VARIANT_COUNT] = {0, 2, 0, 0, 0, 0};
 int set_variant(int which, int value)
 {
     if (which < 0 || which >= WCE_VARIANT_COUNT || value < 0 || value > 15) return WCE_EINVAL;
@@ -3107,6 +3111,9 @@ int launch_mmse_solve(const State *st, const SolveArgs &a, void *stream)
         }
         return hip_status(hipGetLastError());
     }
+    // rank-1 C: the closed form (wce_rank1.hip); variant 1 keeps the factorisation for A/B
+    if (a.hout && !a.ref_pilots && variant(WCE_VARIANT_R1) != 1)
+        return launch_mmse_rank1(st, a, variant(WCE_VARIANT_R1) == 2, stream);
     if (a.hout) hipLaunchKernelGGL(mmse_solve_fc_kernel, g, b, 0, s, st, a);
     else if (a.cu) hipLaunchKernelGGL(mmse_solve_kernel<true>, g, b, 0, s, st, a);
     else hipLaunchKernelGGL(mmse_solve_kernel<false>, g, b, 0, s, st, a);

@@ -48,10 +48,18 @@ int wce_debug_set_flat_chunk(long long frames);
  * one- / two-workgroups-per-CU build at any size; 2..4: ranks past 8 one
  * frame per wave).  which 4: REF + WCE_MMSE_FRAME_COV in C semantics (0 =
  * ref_fc_kernel, one launch, default; 1 = the LT_LS pass, two matvec
- * launches and the REF read-out).
+ * launches and the REF read-out).  which 5: PS_MMSE with a rank-1
+ * covariance, i.e. TEXTBOOK and WCE_MMSE_FRAME_COV (0 = the closed form,
+ * mmse_rank1_kernel: Ryy is the identity plus rank 1, so two dot products and
+ * a correction sum give H, 16 lanes per (frame, block), default; a call that
+ * also asks for LS outputs or equalization runs the LS pass, then this kernel;
+ * 1 = the 53 x 53 factorisation, mmse_solve_fc_kernel, one wave per (frame,
+ * block), and with LS outputs the fused mmse_solve_ls_kernel; 2 = the closed
+ * form with nontemporal loads and stores).
  * Process-wide; the variants of which 0, 1, 2, 4 give bit-identical results,
  * which 3's kernels sum in different orders and agree to rounding (tests
- * check both).  (Round 4 retired ls_flat_kernel -- which 1 = 0, 1 -- and the
+ * check both); which 5's 0 and 2 are bit-identical, 0 and 1 agree to ~1e-11
+ * (both within 1e-10 of the long double closed form).  (Round 4 retired ls_flat_kernel -- which 1 = 0, 1 -- and the
  * REF frame tiles -- which 0 = 1.) */
 int wce_debug_set_variant(int which, int value);
 /* WCE_MMSE_COV solve form for A/B and accuracy probes: 0 = as the state

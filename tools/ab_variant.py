@@ -1,7 +1,9 @@
 """Interleaved A/B of kernel variants (wce_debug_set_variant) on the same
 buffers in one process: rounds x (variant a, variant b, ...), HIP-event
 timing per launch, outputs compared bit for bit across variants.
-usage: python tools/ab_variant.py {ref,ls,dense} [--variants 0 1] [--rounds 5] [--reps 20]"""
+usage: python tools/ab_variant.py {ref,ls,dense,rank1} [--variants 0 1] [--rounds 5] [--reps 20]
+rank1: the TEXTBOOK headline under WCE_VARIANT_R1 (0 closed form, 1 factorisation, 2 closed form, nontemporal);
+0 and 2 are bit-identical, 1 agrees to rounding."""
 import argparse
 import importlib
 import os
@@ -13,7 +15,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
 N, NBLK = 53, 15
-WHICH = {"ref": 0, "ls": 1, "dense": 2, "headline": 3}
+WHICH = {"ref": 0, "ls": 1, "dense": 2, "headline": 3, "rank1": 5}
 
 
 def main():
@@ -42,7 +44,7 @@ def main():
         o = wce.Outputs(None, None, None, None, H.addr, None, N, 0, 0, 0, 0)
         run = lambda: ctx.estimate(fr, o, wce.PS_MMSE, s)
         alg, unit = bench.BYTES_REF_ALG, "alg"
-    elif args.leg == "headline":
+    elif args.leg in ("headline", "rank1"):
         ctx = wce.Context(inp["tx_pre"], inp["rx_pre"], inp["ow2"], wce.MMSE_TEXTBOOK)
         hlt = ctx.shared()[0]
         tx, rx = wce.DeviceArray((n, NBLK, N)), wce.DeviceArray((n, NBLK, N))
@@ -53,6 +55,8 @@ def main():
         o = wce.Outputs(None, None, None, None, H.addr, None, N, 0, 0, 0, 0)
         run = lambda: ctx.estimate(fr, o, wce.PS_MMSE, s)
         alg, unit = bench.FLOP_SOLVE_TXT / 1000.0 + bench.FLOP_APPLY / 1000.0, "(= PF/s of F_alg)"
+        if args.leg == "rank1":
+            alg, unit = 3.0 * N * 16, "of the 2,544 B per frame (tx block, rx block, H)"
     elif args.leg == "dense":
         # COV mode (full-rank PDP covariance): the dense solve alone (W = X z)
         import prof_leg

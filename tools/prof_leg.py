@@ -4,14 +4,15 @@ workload for rocprofv3 --pmc passes (tools/pmc_legs.sh), so that a per-kernel
 average over the dispatches of a pass is an average over same-size launches.
 
 legs (bench.py field -> kernel, frames per launch):
-  headline   roofline            mmse_solve_fc_kernel             65,536 (TEXTBOOK, 1 wave/frame)
+  headline   roofline            mmse_rank1_kernel<false>         65,536 (TEXTBOOK closed form, 16 lanes/frame)
   apply      apply_kernel        apply_kernel                     65,536 (COV H = C W, persistent since round 5)
   cov_solve  cov_mode            mmse_solve_kernel<false>         65,536 (COV dense solve)
   ref        ref_mode.b1048576   mmse_ref_elem_kernel          1,048,576 (REF, main.c semantics)
   ls         ls_config2          ls_flat_kernel                1,048,576 (LT_LS + PS_Linear)
   ls_pilots  (calibration)       ls_flat_kernel                1,048,576 (PS_Linear only: pilot reads)
   front_*    front_end           front_kernel<false/true>         65,536 frames (x 15 blocks / 1 LTF)
-  config5    config5_sharded     mmse_solve_ls_kernel<true,true,true>  1,048,576 (all 5 + eq, fp32 LS)
+  config5    config5_sharded     ls_kernel<true,false,false>   1,048,576 (all 5 + eq, fp32 LS: the LS pass, then
+                                 mmse_rank1_kernel; the LS pass moves 9/10 of the bytes)
   config5_ref(_f32) config5_ref   ref_ls_elem_kernel<true>      1,048,576 (REF + LS family + eq, fp64 / fp32 LS)
   config5_ref_fc(_factors)       ref_ls_elem_kernel<true> / ref_fc_kernel<false>  1,048,576 (the same | FRAME_COV)
   frame_cov_ref frame_cov.ref    ref_fc_kernel<false>             65,536 (REF PS_MMSE | FRAME_COV: one launch)
@@ -32,7 +33,7 @@ sys.path.insert(0, REPO)
 N, NBLK = 53, 15
 
 LEGS = {
-    "headline": ("mmse_solve_fc_kernel", 65536),
+    "headline": ("mmse_rank1_kernel<false>", 65536),   # the closed-form rank-1 solve (wce_rank1.hip)
     "apply": ("apply_kernel", 65536),                # round 5: the streaming kernel at every size
     "apply1m": ("apply_kernel", 1 << 20),             # the same at configs[3]'s batch
     "cov_solve": ("mmse_solve_kernel<false>", 65536),
@@ -41,7 +42,7 @@ LEGS = {
     "ls_pilots": ("ls_elem_kernel", 1 << 20),      # PS_Linear only: calibrates the pilot-sector reads
     "front_blocks": ("front_kernel<false>", 65536),
     "front_preamble": ("front_kernel<true>", 65536),
-    "config5": ("mmse_solve_ls_kernel<true, true, true>", 1 << 20),
+    "config5": ("ls_kernel<true, false, false>", 1 << 20),   # two passes since the closed form: LS, then mmse_rank1_kernel
     "config5_ref": ("ref_ls_elem_kernel<true>", 1 << 20),
     "config5_ref_f32": ("ref_ls_elem_kernel<true>", 1 << 20),
     "config5_ref_fc": ("ref_ls_elem_kernel<true>", 1 << 20),          # REF + FRAME_COV, all 5 + eq (round 4) ...
