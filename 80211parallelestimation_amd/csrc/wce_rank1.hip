@@ -14,6 +14,12 @@
 // 6 digits at cond(Ryy) = 4e6 (9.5e-10 norm-relative on BPSK frames against
 // 5e-16 for this form; tests/test_rank1_model.py).  H = u s.
 //
+// A given w (SolveArgs::cw, rank1_s's cwg) comes from REF with the border dot
+// off under WCE_MMSE_FRAME_COV only, where a = 0 and so g = 0
+// (tests/test_rank1_routes_gpu.py).  g != 0 with a given w has no caller today:
+// that arithmetic is pinned by the CPU model alone (tests/test_rank1_model.py
+// against the mpmath fixture tests/golden/rank1_cw_mp.npz).
+//
 // 16 lanes per (frame, block) unit, 16 units per 256-thread workgroup.  Lane i
 // owns subcarriers i, i + 16, i + 32, i + 48 (< 53): every load and store
 // instruction moves 256 contiguous bytes of a frame.  The three sums are

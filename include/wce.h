@@ -60,7 +60,9 @@ enum {
  * (wce_frames.rx_pre required) instead of the context's shared preamble, i.e.
  * main.c's PS_MMSE called with H_EST_LS = that frame's LT_LS (main.c:41-53 per
  * frame).  C_f = F Rhh_f F^H is rank 1, so it is never formed: two batched
- * MFMA matrix-vector products give its factors and the solve writes H. */
+ * MFMA matrix-vector products give its factors and the solve writes H.  On a
+ * WCE_MMSE_COV context the modifier replaces the model covariance: the request
+ * gives what a TEXTBOOK context on the same preamble gives, bit for bit. */
 #define WCE_MMSE_FRAME_COV (1u << 6)
 
 /* MMSE semantics (DESIGN.md "MMSE contract"):

@@ -1,8 +1,12 @@
 """BASELINE configs[4] as named, at full size on one GPU: 1,048,576 frames,
-all 5 estimators + per-symbol equalization fused into the MMSE solve
-(mmse_solve_ls_kernel), mixed precision (fp64 solve; LT_LS / PS_Linear /
-PS_Cubic / PS_Sinc and the equalized symbols stored as complex float,
-WCE_OUT_LS_F32), per-frame preambles, frames with their own channels.
+all 5 estimators + per-symbol equalization, mixed precision (fp64 solve;
+LT_LS / PS_Linear / PS_Cubic / PS_Sinc and the equalized symbols stored as
+complex float, WCE_OUT_LS_F32), per-frame preambles, frames with their own
+channels.  Since the closed-form rank-1 solve this request runs the LS pass
+(ls_kernel), then mmse_rank1_kernel; the fusion into the MMSE solve
+(mmse_solve_ls_kernel) runs behind wce_debug_set_variant(5, 1) only and is
+tested by tests/test_rank1_routes_gpu.py (the "all" and "all_f32" requests in
+C semantics, variant 1), not here.
 
 Checks (main.c:66-212, WiFi_Equalization.m:1-9):
   * every output of every frame is finite (wce_nonfinite_scan);

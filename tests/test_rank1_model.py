@@ -24,7 +24,21 @@ double (4e6 x 5e-20).  Against the split form evaluated in long double the
 model is at 3.6e-16 / 2.3e-15 on BPSK and unchanged elsewhere.  The complex
 matched cases are the form's own: rx_k - al_k t is a difference of nearly
 equal fp64 numbers there, ~eps cond / sqrt(live subcarriers).
+
+The branch for a given w (`cwg`: complex g, complex division) has no caller
+with g != 0, so `model_s(..., cwg=True)` is pinned against mpmath instead
+(tests/golden/make_rank1_cw_mp.py: the 53 x 53 matrix inverted by LU at 50
+digits, w = conj(u) with phases turned by up to 0.3 rad and amplitudes scaled
+by up to 20%, x zeroed off the mask as `masked` does).  Maxima, relative in
+s, 4 frames per class at the same operating point:
+
+    BPSK   matched 1.0e-16   unrelated 2.7e-16
+    QPSK   matched 5.6e-13   unrelated 2.6e-15
+    16-QAM matched 4.9e-13   unrelated 1.4e-15
+    a = 0, the four pilots in the mask (REF's shape): 5.1e-16
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -92,6 +106,11 @@ def model_s(x, r, u, w, ac, bc, cwg=False):
     s = (t[0] + c[0] / bc, t[1] + c[1] / bc)
     assert np.array_equal(s[0], s[0][..., :1].repeat(16, -1)), "every lane holds the same bits"
     return s
+
+
+def masked(x, mask):
+    """x as mmse_rank1_kernel holds it: zero off State::xmask (mask: [..., 53] of 0 / 1); rx is left alone."""
+    return np.where(np.asarray(mask, bool), np.asarray(x, np.complex128), 0.0)
 
 
 def model_h(cvec, tx, rx, ow2):
@@ -195,3 +214,42 @@ def test_null_zero_and_tiny_symbols(setup, oracle):
     err = normrel(got[live], _closed(oracle, c, tx[live], rx[live], inp["ow2"]))
     print(f"\nnull / tiny symbols: max {err.max():.2e}")
     assert err.max() < TOL, err
+
+
+# ---- the given-w branch (cwg) with a nonzero complex g: no public route reaches it
+# (REF, its only caller, has a = 0), so the arithmetic is pinned here only
+CW_PINS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rank1_cw_mp.npz")
+
+
+def test_given_w_branch_against_mpmath():
+    """model_s(..., cwg=True) against tests/golden/make_rank1_cw_mp.py: the 53 x 53
+    matrix a diag(x) u w^T diag(x)^H + b I inverted by LU in mpmath at 50 digits,
+    w a non-conjugate vector, plus REF's shape (a = 0, pilots only).  1e-10
+    relative in s; the same algebra in long double stays below 1.3e-11 over 500
+    frames per class, so the bound leaves the reference's own error out."""
+    p = np.load(CW_PINS)
+    tx, rx, mask, cls = p["tx"], p["rx"], p["mask"], p["cls"]
+    n = tx.shape[0]
+    assert n == 28 and len(p["cls_name"]) == 7
+    assert np.all(p["a"][cls == 6] == 0.0) and np.all(mask[cls == 6].sum(-1) == 4), "the REF-shaped class"
+    assert np.all(mask[cls < 6] == 1) and np.all(p["a"][cls < 6] == 1.0)
+    u = _lanes(np.broadcast_to(p["u"], (n, N)))
+    w = _lanes(p["w"][cls])
+    assert np.abs(p["w"] - p["u"].conj()).max() > 0.05 * np.abs(p["u"]).max(), "w is not conj(u)"
+    with np.errstate(all="ignore"):
+        s = model_s(_lanes(masked(tx, mask)), _lanes(rx), u, w, p["a"][:, None], p["b"][:, None], cwg=True)
+    got = (s[0][:, 0] + 1j * s[1][:, 0]).astype(np.clongdouble)
+    ref = p["s_hi"].astype(np.clongdouble) + p["s_lo"].astype(np.clongdouble)
+    err = np.asarray(np.abs(got - ref) / np.abs(ref), np.float64)
+    for ci, nm in enumerate(p["cls_name"]):
+        print(f"\n{nm}: max {err[cls == ci].max():.2e}", end="")
+    assert err.max() < TOL, (int(err.argmax()), err.max())
+    # the mask matters: with x left whole off the pilots the REF-shaped class moves
+    with np.errstate(all="ignore"):
+        s2 = model_s(_lanes(tx), _lanes(rx), u, w, p["a"][:, None], p["b"][:, None], cwg=True)
+    assert not np.array_equal(s2[0][cls == 6], s[0][cls == 6])
+    # and so does the branch: the real-g form on the same inputs is far off
+    with np.errstate(all="ignore"):
+        s3 = model_s(_lanes(masked(tx, mask)), _lanes(rx), u, w, p["a"][:, None], p["b"][:, None], cwg=False)
+    g3 = (s3[0][:, 0] + 1j * s3[1][:, 0]).astype(np.clongdouble)
+    assert np.asarray(np.abs(g3 - ref) / np.abs(ref), np.float64)[cls < 6].min() > 1e-6
