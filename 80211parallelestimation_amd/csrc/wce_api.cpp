@@ -373,13 +373,10 @@ static wce::SolveArgs solve_args(const wce_ctx *c, const wce_frames *in, wce_com
         a.cu = c->d_state->cvec;
         a.cw = nullptr;
         a.cs = 0;
-        a.hout = c->bdot;
     } else if (c->mode == WCE_MMSE_REF && c->bdot) {   // C_ref = u w^T (a = 0: no Ryy build)
         a.cu = c->d_state->cvec;
         a.cw = c->d_state->cwvec;
         a.cs = 0;
-        a.hout = 1;
-        a.ref_pilots = 1;   // Ryy = 2 ow2 I, X = pilots: s = w^T X rx / b from 4 subcarriers
     }
     a.tx = reinterpret_cast<const double *>(in->tx);
     a.rx = reinterpret_cast<const double *>(in->rx);
@@ -406,12 +403,11 @@ int wce_mmse_solve(wce_ctx *c, const wce_frames *in, wce_complex *W, int64_t w_s
         return fail(WCE_EINVAL, "wce_mmse_solve: this WCE_MMSE_COV ctx runs the low-rank path (H = U s, no W / apply "
                                 "stages); use wce_estimate");
     wce::SolveArgs a = solve_args(c, in, W, w_stride);
-    if (a.hout) {   // the profiling pair solve -> apply keeps W = X z: rank-1 build only
-        a.hout = 0;
-        if (c->mode != WCE_MMSE_TEXTBOOK) a.cu = a.cw = nullptr;
-    }
+    // the profiling pair solve -> apply keeps W = X z: TEXTBOOK the rank-1 build, the rest the dense C
+    const bool r1 = c->mode == WCE_MMSE_TEXTBOOK;
+    if (!r1) a.cu = a.cw = nullptr;
     DeviceGuard g(c->device);
-    rc = wce::launch_mmse_solve(c->d_state, a, stream);
+    rc = wce::launch_mmse_factor(c->d_state, a, r1 ? wce::SolveForm::Rank1Build : wce::SolveForm::Dense, stream);
     return rc ? fail(rc, "mmse_solve launch") : WCE_OK;
 }
 
@@ -520,58 +516,41 @@ int wce_ctx_reserve(wce_ctx *c, int64_t n)
     return wce_ctx_reserve_stream(c, n, nullptr);
 }
 
-// WCE_MMSE_FRAME_COV: H_LT_f -> factors u_f, w_f of C_f (MFMA matvec, and for
-// REF the folded pilot-row map), into the solve arguments.  lt_ready: the
-// caller's LT_LS output already holds H_LT.  REF in C semantics takes one
-// launch (ref_fc_kernel) that writes H = u s itself and sets *done.
-// REF in C semantics runs ref_fc_kernel: one launch, no workspace.  The fused
-// LS epilogue after it must be ref_ls_elem_kernel (the default REF_LS form);
-// the wave-per-frame form takes the general path.
-static bool ref_fc_path(const wce_ctx *c, const wce_frames *in, const wce::SolveArgs &sa)
-{
-    return c->mode == WCE_MMSE_REF && sa.ref_pilots && in->semantics == WCE_SEM_C &&
-           wce::variant_value(wce::WCE_VARIANT_REF_FC) == 0 && wce::variant_value(wce::WCE_VARIANT_REF_LS) == 0;
-}
-
-static int prep_frame_cov(wce_ctx *c, const wce_frames *in, const wce_outputs *out, bool lt_ready,
-                          wce::SolveArgs &sa, double *ws, bool *done, void *stream)
+// WCE_MMSE_FRAME_COV: the route's preparation step.  RefFc writes H itself;
+// FcU and General put the factors u_f (and, REF, w_f) of C_f into the
+// workspace and into the solve arguments.
+static int prep_frame_cov(wce_ctx *c, const wce_frames *in, const wce_outputs *out, const wce::Route &r,
+                          wce::SolveArgs &sa, double *ws, void *stream)
 {
     const int64_t n = in->n_frames;
-    if (!in->rx_pre) return fail(WCE_EINVAL, "WCE_MMSE_FRAME_COV needs per-frame preambles (rx_pre)");
-    int rc = WCE_OK;
     const State *st = c->d_state;
-    *done = false;
-    if (ref_fc_path(c, in, sa)) {
-        rc = wce::launch_ref_fc(st, sa, reinterpret_cast<const double *>(in->rx_pre), in->pre_stride,
-                                reinterpret_cast<const double *>(in->tx_pre), stream);
-        if (rc) return fail(rc, "ref_fc launch (frame covariance)");
-        *done = true;
-        return WCE_OK;
+    const double *rx_pre = reinterpret_cast<const double *>(in->rx_pre);
+    const double *tx_pre = reinterpret_cast<const double *>(in->tx_pre);
+    int rc = WCE_OK;
+    if (r.prep == wce::FcPrep::RefFc) {
+        rc = wce::launch_ref_fc(st, sa, rx_pre, in->pre_stride, tx_pre, stream);
+        return rc ? fail(rc, "ref_fc launch (frame covariance)") : WCE_OK;
     }
     if (!ws) return fail(WCE_EINVAL, "frame covariance workspace missing");
     double *hw = ws, *uw = hw + n * WS_LD * 2, *ww = uw + n * WS_LD * 2;
-    if (c->mode == WCE_MMSE_TEXTBOOK && in->semantics == WCE_SEM_C && !lt_ready &&
-        wce::variant_value(wce::WCE_VARIANT_REF_FC) == 0) {   // LT_LS and u = Mu h in one launch
-        rc = wce::launch_fc_u(st, reinterpret_cast<const double *>(in->rx_pre), in->pre_stride,
-                              reinterpret_cast<const double *>(in->tx_pre), uw, WS_LD, n, stream);
-        if (rc) return fail(rc, "fc_u launch (frame covariance)");
-        sa.cu = uw;
-        sa.cw = nullptr;
-        sa.cs = WS_LD;
-        sa.hout = 1;
-        return WCE_OK;
+    sa.cu = uw;
+    sa.cw = r.fc_ref_w ? ww : nullptr;
+    sa.cs = WS_LD;
+    if (r.prep == wce::FcPrep::FcU) {   // LT_LS and u = Mu h in one launch
+        rc = wce::launch_fc_u(st, rx_pre, in->pre_stride, tx_pre, uw, WS_LD, n, stream);
+        return rc ? fail(rc, "fc_u launch (frame covariance)") : WCE_OK;
     }
     const double *h = hw;
     int64_t hs = WS_LD;
-    if (lt_ready) {
+    if (r.fc_lt_ready) {   // the caller's LT_LS output already holds H_LT
         h = reinterpret_cast<const double *>(out->lt_ls);
         hs = out->out_stride;
     } else {
         wce::LsArgs a{};
         a.tx = reinterpret_cast<const double *>(in->tx);
         a.rx = reinterpret_cast<const double *>(in->rx);
-        a.rx_pre = reinterpret_cast<const double *>(in->rx_pre);
-        a.tx_pre = reinterpret_cast<const double *>(in->tx_pre);
+        a.rx_pre = rx_pre;
+        a.tx_pre = tx_pre;
         a.fs = in->frame_stride; a.bs = in->block_stride; a.ps = in->pre_stride; a.n = n; a.blk = in->block;
         a.matlab = in->semantics == WCE_SEM_MATLAB;
         a.mask = WCE_EST_LT_LS;
@@ -581,13 +560,27 @@ static int prep_frame_cov(wce_ctx *c, const wce_frames *in, const wce_outputs *o
         if (rc) return fail(rc, "ls launch (H_LT for frame covariance)");
     }
     rc = wce::launch_matvec(st->Mu, nullptr, h, hs, uw, nullptr, WS_LD, n, false, stream);   // u
-    if (!rc && c->mode == WCE_MMSE_REF) rc = wce::launch_ref_w(st, h, hs, ww, WS_LD, n, stream);   // w, pilot rows
-    if (rc) return fail(rc, "matvec launch (frame covariance)");
-    sa.cu = uw;
-    sa.cw = c->mode == WCE_MMSE_REF ? ww : nullptr;
-    sa.cs = WS_LD;
-    sa.hout = 1;
-    return WCE_OK;
+    if (!rc && r.fc_ref_w) rc = wce::launch_ref_w(st, h, hs, ww, WS_LD, n, stream);   // w, pilot rows
+    return rc ? fail(rc, "matvec launch (frame covariance)") : WCE_OK;
+}
+
+// the facts plan_route() decides on; the one place that reads the A/B variants
+static wce::RouteFacts route_facts(const wce_ctx *c, const wce_frames *in, const wce_outputs *out, uint32_t mask)
+{
+    wce::RouteFacts f{};
+    f.mode = c->mode;
+    f.bdot = c->bdot;
+    f.fuse = c->fuse;
+    f.cm = c->cm_on && c->cm_use;
+    f.lr_k0 = cov_lr_k0(c);
+    f.cov_rank = c->cov_rank;
+    f.semantics = in->semantics;
+    f.mask = mask;
+    f.ls_f32 = (out->flags & WCE_OUT_LS_F32) != 0;
+    f.r1 = wce::variant_value(wce::WCE_VARIANT_R1);
+    f.ref_fc = wce::variant_value(wce::WCE_VARIANT_REF_FC);
+    f.ref_ls = wce::variant_value(wce::WCE_VARIANT_REF_LS);
+    return f;
 }
 
 // fixed != nullptr: a plan's own workspace (capture time); otherwise the
@@ -624,36 +617,19 @@ static int estimate_impl(wce_ctx *c, const wce_frames *in, const wce_outputs *ou
     if ((mask & WCE_MMSE_FRAME_COV) && !in->rx_pre)
         return fail(WCE_EINVAL, "WCE_MMSE_FRAME_COV needs per-frame preambles (rx_pre)");
     DeviceGuard g(c->device);
-    const bool ls = (mask & (WCE_EST_LS_ALL | WCE_EQUALIZE)) != 0;
-    const bool mmse = (mask & WCE_EST_PS_MMSE) != 0;
-    // Config-5 fusion: the LS family and equalization ride in the MMSE solve's
-    // epilogue (C semantics); otherwise one HBM-streaming LS pass.
-    const int lr_k0 = (mask & WCE_MMSE_FRAME_COV) ? -1 : cov_lr_k0(c);   // WCE_MMSE_COV low-rank path
-    // constant-modulus frames on the shared operator K (wce_ctx_set_modulus), the
-    // rest on the per-frame kernels, which skip the flagged frames.  Not for ranks
-    // 1..8 (the lane kernels are already bound by the frames' HBM traffic).
-    const bool cm = mmse && c->mode == WCE_MMSE_COV && c->cm_on && c->cm_use && in->semantics == WCE_SEM_C &&
-                    !(mask & WCE_MMSE_FRAME_COV) && (lr_k0 < 0 || c->cov_rank > wce::LRL_RMAX);
-    // A rank-1 covariance (TEXTBOOK's shared C, or any per-frame C off REF's pilot form) is solved in closed
-    // form by a kernel bound by the frames' HBM traffic (mmse_rank1_kernel): no VALU-bound solve is left
-    // for the LS traffic to hide under, so such a request runs the LS pass, then that kernel.
-    const bool ref_dot = c->mode == WCE_MMSE_REF && c->bdot;
-    const bool closed = wce::variant_value(wce::WCE_VARIANT_R1) != 1 &&
-                        ((mask & WCE_MMSE_FRAME_COV) ? !ref_dot : (c->mode == WCE_MMSE_TEXTBOOK && c->bdot));
-    const bool fuse = c->fuse && ls && mmse && in->semantics == WCE_SEM_C && lr_k0 < 0 && !cm && !closed;
+    const wce::Route r = wce::plan_route(route_facts(c, in, out, mask));
     const wce::LsArgs la = ls_args(in, out, mask, eq_src);
-    if (ls && !fuse) {
+    if (r.ls_pass) {
         rc = wce::launch_ls(c->d_state, la, stream);
         if (rc) return fail(rc, "ls launch");
     }
-    if (!mmse) return WCE_OK;
+    if (!(mask & WCE_EST_PS_MMSE)) return WCE_OK;
     wce::SolveArgs sa = solve_args(c, in, out->ps_mmse, out->out_stride);
-    const bool fc = (mask & WCE_MMSE_FRAME_COV) != 0;
     const bool split = sa.nblk > 1;   // MATLAB: one wave per (frame, block), averaged after
     if (split && n * sa.nblk > INT32_MAX) return fail(WCE_EINVAL, "n_frames * 4 > 2^31 - 1 (MATLAB semantics)");
     std::unique_lock<std::mutex> lk;
     double *ws = nullptr;
-    if ((fc && !ref_fc_path(c, in, sa)) || split || cm) {
+    if (r.workspace) {
         wce::Workspace *w = fixed;
         if (!w) {
             w = stream_ws(c, stream, lk);
@@ -670,22 +646,14 @@ static int estimate_impl(wce_ctx *c, const wce_frames *in, const wce_outputs *ou
         }
         ws = w->p;
     }
-    if (fc) {
-        const bool lt_ready = !fuse && (mask & WCE_EST_LT_LS) && !(out->flags & WCE_OUT_LS_F32);
-        bool done = false;   // REF, C semantics: H written by the factor launch itself
-        rc = prep_frame_cov(c, in, out, lt_ready, sa, ws, &done, stream);
+    if (r.prep != wce::FcPrep::None) {
+        rc = prep_frame_cov(c, in, out, r, sa, ws, stream);
         if (rc) return rc;
-        if (done && !fuse) return WCE_OK;
-        if (done) {   // the LS family + equalization still ride the one-element-per-thread pass
-            sa.mmse_done = 1;
-            rc = wce::launch_mmse_solve_ls(c->d_state, sa, la, stream);
-            return rc ? fail(rc, "ls epilogue launch") : WCE_OK;
-        }
     }
     double *aux = ws ? ws + (WS_ARRAYS - 1) * n * WS_LD * 2 : nullptr;
     if (split) {
         sa.split = 1;
-        if (sa.hout) {
+        if (r.form == wce::SolveForm::Bordered) {   // the per-block dots, averaged by fc_finish
             sa.dots = aux;
         } else {
             sa.w = ws;
@@ -693,25 +661,44 @@ static int estimate_impl(wce_ctx *c, const wce_frames *in, const wce_outputs *ou
         }
     }
     double *H = reinterpret_cast<double *>(out->ps_mmse);
-    if (cm) {   // flags (one byte per frame) in the aux array, unused in C semantics
+    if (r.cm) {   // flags (one byte per frame) in the aux array, unused in C semantics
         uint8_t *flags = reinterpret_cast<uint8_t *>(aux);
         rc = wce::launch_cm(c->d_state, sa, flags, stream);
         if (rc) return fail(rc, "constant-modulus launch");
         sa.skip = flags;
     }
-    if (lr_k0 >= 0) {   // H = U s straight from the solve (split: H_b rows, then the block mean)
-        rc = wce::launch_mmse_lr(c->d_state, lr_k0, c->cov_rank, c->cov_taps, sa, stream);
+    const State *st = c->d_state;
+    switch (r.solve) {
+    case wce::SolveStep::None: return WCE_OK;
+    case wce::SolveStep::RefLsElemDone:   // the LS family + equalization still ride the one-element-per-thread pass
+        rc = wce::launch_ref_ls_elem(st, sa, la, true, stream);
+        return rc ? fail(rc, "ls epilogue launch") : WCE_OK;
+    case wce::SolveStep::LowRank:
+        rc = wce::launch_mmse_lr(st, cov_lr_k0(c), c->cov_rank, c->cov_taps, sa, stream);
         if (rc) return fail(rc, "mmse_lr launch");
-        if (split) rc = wce::launch_avg_blocks(ws, WS_LD, H, out->out_stride, n, stream);
-        return rc ? fail(rc, "block average launch") : WCE_OK;
+        break;
+    case wce::SolveStep::RefPilots: rc = wce::launch_mmse_ref_pilots(st, sa, stream); break;
+    case wce::SolveStep::RefLsElem: rc = wce::launch_ref_ls_elem(st, sa, la, false, stream); break;
+    case wce::SolveStep::Closed: rc = wce::launch_mmse_rank1(st, sa, false, stream); break;
+    case wce::SolveStep::ClosedNt: rc = wce::launch_mmse_rank1(st, sa, true, stream); break;
+    case wce::SolveStep::Factor: rc = wce::launch_mmse_factor(st, sa, r.form, stream); break;
+    case wce::SolveStep::Fused: rc = wce::launch_mmse_solve_ls(st, sa, la, r.form, stream); break;
     }
-    rc = fuse ? wce::launch_mmse_solve_ls(c->d_state, sa, la, stream) : wce::launch_mmse_solve(c->d_state, sa, stream);
     if (rc) return fail(rc, "mmse_solve launch");
-    if (sa.hout && split) rc = wce::launch_fc_finish(sa, aux, H, out->out_stride, stream);
-    else if (split) rc = wce::launch_matvec_avg(c->d_state->C, ws, WS_LD, sa.nblk, H, out->out_stride, n, stream);
-    else if (!sa.hout) rc = wce::launch_mmse_apply(c->d_state, H, H, out->out_stride, n, stream, sa.skip);   // H = C W in place
-    if (rc) return fail(rc, "mmse apply launch");
-    return WCE_OK;
+    switch (r.finish) {
+    case wce::Finish::None: break;
+    case wce::Finish::AvgBlocks:
+        rc = wce::launch_avg_blocks(ws, WS_LD, H, out->out_stride, n, stream);
+        return rc ? fail(rc, "block average launch") : WCE_OK;
+    case wce::Finish::FcFinish: rc = wce::launch_fc_finish(sa, aux, H, out->out_stride, stream); break;
+    case wce::Finish::MatvecAvg:
+        rc = wce::launch_matvec_avg(st->C, ws, WS_LD, sa.nblk, H, out->out_stride, n, stream);
+        break;
+    case wce::Finish::Apply:   // H = C W in place
+        rc = wce::launch_mmse_apply(st, H, H, out->out_stride, n, stream, sa.skip);
+        break;
+    }
+    return rc ? fail(rc, "mmse apply launch") : WCE_OK;
 }
 
 int wce_estimate(wce_ctx *c, const wce_frames *in, const wce_outputs *out, uint32_t mask, void *stream)
@@ -738,8 +725,8 @@ int wce_plan_create(wce_plan **out_plan, wce_ctx *c, const wce_frames *in, const
     if (!p) return fail(WCE_ENOMEM, "alloc");
     p->device = c->device;
     // size the plan's workspace now: nothing may allocate while the stream is captured
-    if ((mask & WCE_MMSE_FRAME_COV) || (in->semantics == WCE_SEM_MATLAB && (mask & WCE_EST_PS_MMSE)) ||
-        (c->mode == WCE_MMSE_COV && c->cm_on && (mask & WCE_EST_PS_MMSE))) {
+    // (exactly when estimate_impl will use it; a request it rejects allocates nothing it needs)
+    if (wce::plan_route(route_facts(c, in, out, mask)).workspace) {
         int rc = grow_ws(c, p->ws, in->n_frames > 0 ? in->n_frames : 1, nullptr);
         if (rc) { delete p; return rc; }
     }

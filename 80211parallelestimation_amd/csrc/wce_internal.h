@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/wce.h"
+#include "wce_route.h"
 
 namespace wce {
 
@@ -161,6 +162,9 @@ struct LsArgs {
     uint32_t eq_src;
     uint32_t pad;
 };
+// Data of one solve launch, copied into every solve kernel's arguments: buffers,
+// strides and the unit layout.  Which kernel family reads it is the route's
+// business (wce_route.h), not this struct's.
 struct SolveArgs {
     const double *tx, *rx;
     int64_t fs, bs, n;
@@ -172,14 +176,11 @@ struct SolveArgs {
     // stride cs (0: one shared pair); cw == null: cw_f = conj(cu_f).
     const double *cu, *cw;
     int64_t cs;
-    int32_t hout;             // 1: write H = cu (cw . W) directly (no apply step)
     int32_t split;            // MATLAB averaging: nblk waves per frame, wave g = f*nblk + b
-                              // writes W_b to w[g*ws] (or, with hout, cw . W_b to dots[g])
+                              // writes W_b to w[g*ws] (or, in the bordered form, cw . W_b to dots[g])
     double *dots;
-    int32_t ref_pilots;       // REF (main.c): a = 0 and X = the 4 pilots -> mmse_ref_flat_kernel
-    int32_t mmse_done;        // H already written (REF frame covariance): the fused launch runs the LS family only.
-                              // Honoured ONLY by launch_mmse_solve_ls's REF element path (ref_ls_elem_kernel);
-                              // every other SolveArgs launcher returns WCE_EINVAL when it is set
+    int32_t mmse_done;        // ref_ls_elem_kernel only, set by launch_ref_ls_elem: H already written (REF
+                              // frame covariance), the launch runs the LS family only
     const uint8_t *skip;      // per unit: nonzero = H already written (constant-modulus path); null = none
 };
 struct SynthArgs {
@@ -202,11 +203,19 @@ struct FrontArgs {
 
 int launch_ls(const State *st, const LsArgs &a, void *stream);
 int launch_front(const FrontArgs &a, bool preamble, void *stream);
-int launch_mmse_solve(const State *st, const SolveArgs &a, void *stream);
-// the closed-form rank-1 solve (wce_rank1.hip): every hout && !ref_pilots request of launch_mmse_solve
+// PS_MMSE solve launchers: each starts the one kernel family the route (wce_route.h) names.
+// REF pilot form, C semantics (mmse_ref_flat_kernel / mmse_ref_elem_kernel by batch size)
+int launch_mmse_ref_pilots(const State *st, const SolveArgs &a, void *stream);
+// the 53 x 53 factorisation: Bordered mmse_solve_fc_kernel, Rank1Build mmse_solve_kernel<true>,
+// Dense mmse_solve_kernel<false>
+int launch_mmse_factor(const State *st, const SolveArgs &a, SolveForm form, void *stream);
+// the closed-form bordered rank-1 solve (wce_rank1.hip); nt: nontemporal loads and stores
 int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, void *stream);
-// solve + LS family + equalization of each frame in one launch (C semantics, one block)
-int launch_mmse_solve_ls(const State *st, const SolveArgs &a, const LsArgs &l, void *stream);
+// the same factorisation + LS family + equalization of each frame in one launch (C semantics, one block)
+int launch_mmse_solve_ls(const State *st, const SolveArgs &a, const LsArgs &l, SolveForm form, void *stream);
+// REF pilot form + LS family + equalization, one element per thread; mmse_done: H is already
+// written (ref_fc_kernel), only the LS family and equalization run
+int launch_ref_ls_elem(const State *st, const SolveArgs &a, const LsArgs &l, bool mmse_done, void *stream);
 int launch_mmse_apply(const State *st, const double *W, double *H, int64_t stride, int64_t n, void *stream,
                       const uint8_t *skip = nullptr);
 // constant-modulus frames of a WCE_MMSE_COV batch (C semantics): H = K (conj x o rx)
@@ -243,7 +252,9 @@ int launch_ref_w(const State *st, const double *X, int64_t xs, double *W, int64_
 // H[f] = mean of X rows 4f .. 4f+3 (MATLAB block average, left to right)
 int launch_avg_blocks(const double *X, int64_t xs, double *H, int64_t hs, int64_t n, void *stream);
 int set_flat_chunk(int64_t frames);   // wce_debug_set_flat_chunk
-// kernel variants for A/B timing (wce_debug_set_variant)
+// kernel variants for A/B timing (wce_debug_set_variant).  REF, LS and LR choose among one
+// family's builds inside its launcher; REF_LS, REF_FC and R1 choose the family: they are
+// facts of plan_route() (wce_route.h), read once per call in wce_api.cpp's route_facts()
 constexpr int WCE_VARIANT_REF = 0;    // REF PS_MMSE: 0 = by batch size (default: one element per thread,
                                       // mmse_ref_elem_kernel, past REF_ELEM_FROM frames, else 512-element
                                       // chunks on a capped grid, mmse_ref_flat_kernel), 1 = always the capped
@@ -252,7 +263,8 @@ constexpr int WCE_VARIANT_REF = 0;    // REF PS_MMSE: 0 = by batch size (default
 constexpr int WCE_VARIANT_LS = 1;     // configs[1] LS: 2 = one element per thread (ls_elem_kernel, default),
                                       // 3 = the per-frame LIGHT ls_kernel
 constexpr int WCE_VARIANT_REF_LS = 2;  // REF PS_MMSE + LS family (+ eq), C semantics: 0 = ref_ls_elem_kernel
-                                      // (one element per thread, default), 1 = mmse_solve_ls_kernel (wave per frame)
+                                      // (one element per thread, default), 1 = mmse_solve_ls_kernel (wave per frame;
+                                      // REF + WCE_MMSE_FRAME_COV then takes the general factors)
 constexpr int WCE_VARIANT_LR = 3;     // WCE_MMSE_COV low-rank path: 0 = ranks 1..LRL_RMAX one frame per lane
                                       // (mmse_lr_lane_kernel, direct or LDS-staged by batch size), ranks 9..16
                                       // 16 lanes per frame (mmse_lr_quad_kernel); default

@@ -37,6 +37,12 @@
 //   fc_finish_kernel      MATLAB averaging of the per-block s values.
 //   synth_kernel          counter-RNG synthetic frames (bench / tests).
 // The time-domain front end is in wce_front.hip.
+//
+// Which of these one wce_estimate call runs is decided by plan_route()
+// (wce_route.h), once per call; the launchers at the end of this file each
+// start the one family they are named after and choose only among its builds
+// by batch size or device (REF flat / element, ls_elem / ls_kernel, the
+// low-rank forms).  None of them reads variants R1, REF_FC or REF_LS.
 #include <hip/hip_runtime.h>
 #include "wce_internal.h"
 #include "wce_device.h"
@@ -3082,40 +3088,42 @@ int launch_ls(const State *st, const LsArgs &a, void *stream)
     return hip_status(hipGetLastError());
 }
 
-int launch_mmse_solve(const State *st, const SolveArgs &a, void *stream)
+int launch_mmse_ref_pilots(const State *st, const SolveArgs &a, void *stream)
 {
-    if (a.mmse_done) return WCE_EINVAL;   // only launch_mmse_solve_ls's REF element path honours it
+    if (a.n <= 0) return WCE_OK;
+    if (a.n > 0x7fffffffll) return WCE_EINVAL;
+    if (!a.cu || a.split || a.nblk > 1) return WCE_EINVAL;   // block averaging runs split, on the factorisation
+    hipStream_t s = (hipStream_t)stream;
+    for (int64_t f0 = 0, fc = flat_chunk(); f0 < a.n; f0 += fc) {
+        const int64_t nf = a.n - f0 < fc ? a.n - f0 : fc;
+        // past the MALL one element per thread (elem), inside it the chunks on a
+        // capped grid (flat): 65,536 frames 20.3 / 25.0 us, 131,072 43.1 / 49.2,
+        // 262,144 102.7 / 89.3, 1,048,576 380.9 / 338.7 (flat / elem)
+        const int v = variant(WCE_VARIANT_REF);
+        if (v == 3 || (v == 0 && nf > REF_ELEM_FROM)) {
+            hipLaunchKernelGGL(mmse_ref_elem_kernel, dim3((unsigned)((nf * NSC + 255) / 256)), dim3(256), 0, s, st,
+                               a, f0, (uint32_t)nf);
+            continue;
+        }
+        const int64_t chunks = (nf * NSC + FLAT_CHUNK - 1) / FLAT_CHUNK;
+        int64_t fb = (chunks + LS_WAVES - 1) / LS_WAVES;
+        if (fb > 256 * 8 && v != 2) fb = 256 * 8;
+        hipLaunchKernelGGL(mmse_ref_flat_kernel, dim3((unsigned)fb), dim3(256), 0, s, st, a, f0, (uint32_t)nf);
+    }
+    return hip_status(hipGetLastError());
+}
+
+int launch_mmse_factor(const State *st, const SolveArgs &a, SolveForm form, void *stream)
+{
     if (a.n <= 0) return WCE_OK;
     const int64_t waves = a.split ? a.n * a.nblk : a.n;
     if (waves > 0x7fffffffll) return WCE_EINVAL;
-    if (a.hout && !a.cu) return WCE_EINVAL;
+    if (form != SolveForm::Dense && !a.cu) return WCE_EINVAL;
     if (a.nblk > 1 && !a.split) return WCE_EINVAL;   // block averaging runs split
     const dim3 g((unsigned)waves), b(64);
     hipStream_t s = (hipStream_t)stream;
-    if (a.hout && a.ref_pilots && !a.split) {
-        for (int64_t f0 = 0, fc = flat_chunk(); f0 < a.n; f0 += fc) {
-            const int64_t nf = a.n - f0 < fc ? a.n - f0 : fc;
-            // past the MALL one element per thread (elem), inside it the chunks on a
-            // capped grid (flat): 65,536 frames 20.3 / 25.0 us, 131,072 43.1 / 49.2,
-            // 262,144 102.7 / 89.3, 1,048,576 380.9 / 338.7 (flat / elem)
-            const int v = variant(WCE_VARIANT_REF);
-            if (v == 3 || (v == 0 && nf > REF_ELEM_FROM)) {
-                hipLaunchKernelGGL(mmse_ref_elem_kernel, dim3((unsigned)((nf * NSC + 255) / 256)), dim3(256), 0, s, st,
-                                   a, f0, (uint32_t)nf);
-                continue;
-            }
-            const int64_t chunks = (nf * NSC + FLAT_CHUNK - 1) / FLAT_CHUNK;
-            int64_t fb = (chunks + LS_WAVES - 1) / LS_WAVES;
-            if (fb > 256 * 8 && v != 2) fb = 256 * 8;
-            hipLaunchKernelGGL(mmse_ref_flat_kernel, dim3((unsigned)fb), dim3(256), 0, s, st, a, f0, (uint32_t)nf);
-        }
-        return hip_status(hipGetLastError());
-    }
-    // rank-1 C: the closed form (wce_rank1.hip); variant 1 keeps the factorisation for A/B
-    if (a.hout && !a.ref_pilots && variant(WCE_VARIANT_R1) != 1)
-        return launch_mmse_rank1(st, a, variant(WCE_VARIANT_R1) == 2, stream);
-    if (a.hout) hipLaunchKernelGGL(mmse_solve_fc_kernel, g, b, 0, s, st, a);
-    else if (a.cu) hipLaunchKernelGGL(mmse_solve_kernel<true>, g, b, 0, s, st, a);
+    if (form == SolveForm::Bordered) hipLaunchKernelGGL(mmse_solve_fc_kernel, g, b, 0, s, st, a);
+    else if (form == SolveForm::Rank1Build) hipLaunchKernelGGL(mmse_solve_kernel<true>, g, b, 0, s, st, a);
     else hipLaunchKernelGGL(mmse_solve_kernel<false>, g, b, 0, s, st, a);
     return hip_status(hipGetLastError());
 }
@@ -3196,7 +3204,6 @@ const char *lr_kernel_name(int k0, int rank, int taps, int64_t units)
 
 int launch_mmse_lr(const State *st, int k0, int rank, int taps, const SolveArgs &a, void *stream)
 {
-    if (a.mmse_done) return WCE_EINVAL;
     if (a.n <= 0) return WCE_OK;
     const int64_t waves = a.split ? a.n * a.nblk : a.n;
     if (waves > 0x7fffffffll) return WCE_EINVAL;
@@ -3282,37 +3289,45 @@ int launch_avg_blocks(const double *X, int64_t xs, double *H, int64_t hs, int64_
 
 int launch_fc_finish(const SolveArgs &a, const double *dots, double *H, int64_t hs, void *stream)
 {
-    if (a.mmse_done) return WCE_EINVAL;
     if (a.n <= 0) return WCE_OK;
     hipLaunchKernelGGL(fc_finish_kernel, dim3((unsigned)((a.n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a,
                        dots, H, hs);
     return hip_status(hipGetLastError());
 }
 
-int launch_mmse_solve_ls(const State *st, const SolveArgs &a, const LsArgs &l, void *stream)
+int launch_ref_ls_elem(const State *st, const SolveArgs &a, const LsArgs &l, bool mmse_done, void *stream)
 {
     if (a.n <= 0) return WCE_OK;
-    if (a.hout && !a.cu) return WCE_EINVAL;
-    if (a.mmse_done && !(a.ref_pilots && a.hout && !a.split && variant(WCE_VARIANT_REF_LS) == 0)) return WCE_EINVAL;
+    if (!a.cu || a.split || a.nblk > 1) return WCE_EINVAL;
+    SolveArgs am = a;
+    am.mmse_done = mmse_done;
+    hipStream_t s = (hipStream_t)stream;
+    const bool eq = (l.mask & WCE_EQUALIZE) && l.eq;
+    for (int64_t f0 = 0, fc = flat_chunk(); f0 < a.n; f0 += fc) {   // 53 * frames < 2^32 per launch
+        const int64_t nf = a.n - f0 < fc ? a.n - f0 : fc;
+        const dim3 gb((unsigned)((nf * NSC + 255) / 256));
+        if (eq) hipLaunchKernelGGL(ref_ls_elem_kernel<true>, gb, dim3(256), 0, s, st, am, l, f0, (uint32_t)nf);
+        else hipLaunchKernelGGL(ref_ls_elem_kernel<false>, gb, dim3(256), 0, s, st, am, l, f0, (uint32_t)nf);
+    }
+    return hip_status(hipGetLastError());
+}
+
+int launch_mmse_solve_ls(const State *st, const SolveArgs &a, const LsArgs &l, SolveForm form, void *stream)
+{
+    if (a.n <= 0) return WCE_OK;
+    if (a.n > 0x7fffffffll) return WCE_EINVAL;
+    if (form != SolveForm::Dense && !a.cu) return WCE_EINVAL;
+    if (a.split || a.nblk > 1) return WCE_EINVAL;   // one wave per frame, one block
     const dim3 g((unsigned)a.n), b(64);
     hipStream_t s = (hipStream_t)stream;
     const bool eq = (l.mask & WCE_EQUALIZE) && l.eq;
-    if (a.ref_pilots && a.hout && !a.split && variant(WCE_VARIANT_REF_LS) == 0) {
-        for (int64_t f0 = 0, fc = flat_chunk(); f0 < a.n; f0 += fc) {   // 53 * frames < 2^32 per launch
-            const int64_t nf = a.n - f0 < fc ? a.n - f0 : fc;
-            const dim3 gb((unsigned)((nf * NSC + 255) / 256));
-            if (eq) hipLaunchKernelGGL(ref_ls_elem_kernel<true>, gb, dim3(256), 0, s, st, a, l, f0, (uint32_t)nf);
-            else hipLaunchKernelGGL(ref_ls_elem_kernel<false>, gb, dim3(256), 0, s, st, a, l, f0, (uint32_t)nf);
-        }
-        return hip_status(hipGetLastError());
-    }
 #define WCE_LAUNCH_SLS(R1, HOUT)                                                                        \
     do {                                                                                                \
         if (eq) hipLaunchKernelGGL((mmse_solve_ls_kernel<R1, HOUT, true>), g, b, 0, s, st, a, l);       \
         else hipLaunchKernelGGL((mmse_solve_ls_kernel<R1, HOUT, false>), g, b, 0, s, st, a, l);         \
     } while (0)
-    if (a.hout) WCE_LAUNCH_SLS(true, true);
-    else if (a.cu) WCE_LAUNCH_SLS(true, false);
+    if (form == SolveForm::Bordered) WCE_LAUNCH_SLS(true, true);
+    else if (form == SolveForm::Rank1Build) WCE_LAUNCH_SLS(true, false);
     else WCE_LAUNCH_SLS(false, false);
 #undef WCE_LAUNCH_SLS
     return hip_status(hipGetLastError());
@@ -3856,7 +3871,6 @@ int launch_matvec(const double *M1, const double *M2, const double *X, int64_t x
 int launch_ref_fc(const State *st, const SolveArgs &a, const double *rx_pre, int64_t ps, const double *tx_pre,
                   void *stream)
 {
-    if (a.mmse_done) return WCE_EINVAL;
     if (a.n <= 0) return WCE_OK;
     if (a.split || !rx_pre || !a.w) return WCE_EINVAL;
     const int64_t blocks = tile_blocks((a.n + 15) / 16, APPLY_WAVES * FC_WG_PER_CU);
@@ -3890,7 +3904,6 @@ int launch_ref_w(const State *st, const double *X, int64_t xs, double *W, int64_
 
 int launch_cm(const State *st, const SolveArgs &a, uint8_t *flags, void *stream)
 {
-    if (a.mmse_done) return WCE_EINVAL;
     if (a.n <= 0) return WCE_OK;
     if (a.split || !flags) return WCE_EINVAL;
     const int64_t blocks = (a.n + 16 * APPLY_WAVES - 1) / (16 * APPLY_WAVES);

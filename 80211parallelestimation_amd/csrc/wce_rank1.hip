@@ -138,7 +138,7 @@ __global__ __launch_bounds__(256) void mmse_rank1_kernel(const State *__restrict
 
 int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, void *stream)
 {
-    if (a.mmse_done || !a.hout || !a.cu || a.ref_pilots) return WCE_EINVAL;
+    if (!a.cu) return WCE_EINVAL;
     if (a.split ? !a.dots : !a.w) return WCE_EINVAL;
     if (a.n <= 0) return WCE_OK;
     if (a.nblk > 1 && !a.split) return WCE_EINVAL;

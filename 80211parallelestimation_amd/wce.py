@@ -102,6 +102,7 @@ ABI = {
     "wce_debug_set_variant": [c_int, c_int],
     "wce_debug_set_cov_path": [c_void_p, c_int],
     "wce_debug_lr_kernel": [c_void_p, c_int64],
+    "wce_debug_route": [c_int] * 7 + [c_uint32] + [c_int] * 4 + [ctypes.c_char_p, c_size_t],
     "wce_debug_cov_factor": [c_void_p, c_size_t, c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_double),
                              POINTER(c_double)],
     "wce_ctx_cov_info": [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_double), POINTER(c_double)],
@@ -552,6 +553,15 @@ def state_mode(blob: np.ndarray) -> int:
     m = c_int()
     _check(load().wce_state_validate(blob.ctypes.data_as(c_void_p), blob.nbytes, byref(m)), "wce_state_validate")
     return m.value
+
+
+def debug_route(mode, bdot, fuse, cm, lr_k0, rank, sem, mask, f32, r1, ref_fc, ref_ls) -> str:
+    """The kernel families one estimate call with these facts launches, in order, ';'-separated
+    (wce_debug_route: the route planner alone, no device); raises WceError for facts validation rejects."""
+    buf = ctypes.create_string_buffer(256)
+    _check(load().wce_debug_route(int(mode), int(bdot), int(fuse), int(cm), int(lr_k0), int(rank), int(sem), int(mask),
+                                  int(f32), int(r1), int(ref_fc), int(ref_ls), buf, len(buf)), "wce_debug_route")
+    return buf.value.decode()
 
 
 def cov_factor(blob: np.ndarray):

@@ -2,6 +2,7 @@
  * check the 80-bit shared-state precompute without a GPU. */
 #ifndef WCE_DEBUG_H
 #define WCE_DEBUG_H
+#include <stddef.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -38,7 +39,10 @@ int wce_debug_set_flat_chunk(long long frames);
  * which 1: LT_LS + PS_Linear in C semantics (2 = one element per thread,
  * ls_elem_kernel, default; 3 = the per-frame LIGHT kernel).  which 2: REF
  * PS_MMSE with LS outputs in one call (0 = one element per thread,
- * ref_ls_elem_kernel, default; 1 = the wave-per-frame fused solve).
+ * ref_ls_elem_kernel, default; 1 = the wave-per-frame fused solve, and REF +
+ * WCE_MMSE_FRAME_COV on the general factors).  which 2, 4 and 5 are facts of
+ * the route planner (csrc/wce_route.h, wce_debug_route below): wce_estimate
+ * reads each once per call, and no launcher reads them.
  * which 3: WCE_MMSE_COV low-rank path (0 = ranks 1..8 one frame per lane in
  * the LDS-staged form, mmse_lr_lane_staged_kernel, ranks 7 and 8 in its
  * two-workgroups-per-CU build past 65,536 units on a 256-CU device, and
@@ -46,9 +50,10 @@ int wce_debug_set_flat_chunk(long long frames);
  * rank one frame per wave; 2 = the lane kernel's direct form,
  * mmse_lr_lane_kernel; 3 / 4 = the staged form with ranks 7 and 8 in the
  * one- / two-workgroups-per-CU build at any size; 2..4: ranks past 8 one
- * frame per wave).  which 4: REF + WCE_MMSE_FRAME_COV in C semantics (0 =
- * ref_fc_kernel, one launch, default; 1 = the LT_LS pass, two matvec
- * launches and the REF read-out).  which 5: PS_MMSE with a rank-1
+ * frame per wave).  which 4: WCE_MMSE_FRAME_COV in C semantics (0 = REF
+ * ref_fc_kernel, one launch, TEXTBOOK LT_LS and u in one launch, default;
+ * 1 = the general factors: the LT_LS pass, the matvec launch and, REF, the w
+ * rows, then the solve).  which 5: PS_MMSE with a rank-1
  * covariance, i.e. TEXTBOOK and WCE_MMSE_FRAME_COV (0 = the closed form,
  * mmse_rank1_kernel: Ryy is the identity plus rank 1, so two dot products and
  * a correction sum give H, 16 lanes per (frame, block), default; a call that
@@ -62,6 +67,16 @@ int wce_debug_set_flat_chunk(long long frames);
  * (both within 1e-10 of the long double closed form).  (Round 4 retired ls_flat_kernel -- which 1 = 0, 1 -- and the
  * REF frame tiles -- which 0 = 1.) */
 int wce_debug_set_variant(int which, int value);
+/* The kernel families one wce_estimate call launches, in order, as the route
+ * planner (csrc/wce_route.h) decides them from these facts: the context's mode,
+ * border dot and fusion switches, cm (a constant-modulus operator loaded and
+ * enabled), the WCE_MMSE_COV low-rank block row (-1 dense) and rank, the
+ * request's semantics, mask and WCE_OUT_LS_F32, and variants 5, 4 and 2.
+ * Written to buf as names separated by ';', e.g. "ls;fc_u;mmse_rank1;fc_finish"
+ * ("" for a request that launches nothing).  Needs no device and no context.
+ * WCE_EINVAL for facts wce_estimate's validation rejects, or a short buffer. */
+int wce_debug_route(int mode, int bdot, int fuse, int cm, int lr_k0, int cov_rank, int semantics, unsigned mask,
+                    int ls_f32, int r1, int ref_fc, int ref_ls, char *buf, size_t cap);
 /* WCE_MMSE_COV solve form for A/B and accuracy probes: 0 = as the state
  * chose (default), 1 = always the dense Ryy solve, 2 = always the low-rank
  * Gram path (at the state's rank).  ctx is a wce_ctx*. */

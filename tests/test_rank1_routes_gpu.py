@@ -1,5 +1,6 @@
-"""Every dispatch route into the rank-1 PS_MMSE solve (estimate_impl in
-csrc/wce_api.cpp, launch_mmse_solve / launch_mmse_solve_ls in csrc/wce_kernels.hip):
+"""Every dispatch route into the rank-1 PS_MMSE solve (plan_route in
+csrc/wce_route.cpp decides it, estimate_impl in csrc/wce_api.cpp runs it; which
+kernels each request launches is pinned on the CPU by tests/test_route.py):
 the closed form (mmse_rank1_kernel, WCE_VARIANT_R1 = 0, and its nontemporal
 build, 2) and the retained 53 x 53 factorisation (variant 1: mmse_solve_fc_kernel,
 and mmse_solve_ls_kernel<true, true, *> when the LS family rides along in C
