@@ -565,7 +565,8 @@ static int prep_frame_cov(wce_ctx *c, const wce_frames *in, const wce_outputs *o
 }
 
 // the facts plan_route() decides on; the one place that reads the A/B variants
-static wce::RouteFacts route_facts(const wce_ctx *c, const wce_frames *in, const wce_outputs *out, uint32_t mask)
+static wce::RouteFacts route_facts(const wce_ctx *c, const wce_frames *in, const wce_outputs *out, uint32_t mask,
+                                   bool noise = false)
 {
     wce::RouteFacts f{};
     f.mode = c->mode;
@@ -580,19 +581,27 @@ static wce::RouteFacts route_facts(const wce_ctx *c, const wce_frames *in, const
     f.r1 = wce::variant_value(wce::WCE_VARIANT_R1);
     f.ref_fc = wce::variant_value(wce::WCE_VARIANT_REF_FC);
     f.ref_ls = wce::variant_value(wce::WCE_VARIANT_REF_LS);
+    f.noise = noise;
     return f;
 }
 
 // fixed != nullptr: a plan's own workspace (capture time); otherwise the
-// stream's entry, held locked until the last launch is queued
+// stream's entry, held locked until the last launch is queued.  ow2 != nullptr:
+// wce_estimate_noise's per-frame noise variances (device; never read here)
 static int estimate_impl(wce_ctx *c, const wce_frames *in, const wce_outputs *out, uint32_t mask, void *stream,
-                         wce::Workspace *fixed)
+                         wce::Workspace *fixed, const double *ow2 = nullptr)
 {
     if (!c || !out) return fail(WCE_EINVAL, "null argument");
     if (!c->ready) return fail(WCE_ESTATE, "ctx not ready");
     if (mask & ~0x7Fu) return fail(WCE_EINVAL, "unknown estimator bits");
     if ((mask & WCE_MMSE_FRAME_COV) && !(mask & WCE_EST_PS_MMSE))
         return fail(WCE_EINVAL, "WCE_MMSE_FRAME_COV modifies WCE_EST_PS_MMSE");
+    if (ow2) {
+        if (c->mode != WCE_MMSE_TEXTBOOK)
+            return fail(WCE_EINVAL, "wce_estimate_noise: per-frame ow2 needs a WCE_MMSE_TEXTBOOK context");
+        if (!(mask & WCE_EST_PS_MMSE)) return fail(WCE_EINVAL, "wce_estimate_noise: ow2 given without WCE_EST_PS_MMSE");
+        if (reinterpret_cast<uintptr_t>(ow2) & 7) return fail(WCE_EINVAL, "wce_estimate_noise: ow2 not 8-byte aligned");
+    }
     const bool eq = (mask & WCE_EQUALIZE) != 0;
     int rc = check_frames(in, eq);
     if (rc) return rc;
@@ -617,7 +626,7 @@ static int estimate_impl(wce_ctx *c, const wce_frames *in, const wce_outputs *ou
     if ((mask & WCE_MMSE_FRAME_COV) && !in->rx_pre)
         return fail(WCE_EINVAL, "WCE_MMSE_FRAME_COV needs per-frame preambles (rx_pre)");
     DeviceGuard g(c->device);
-    const wce::Route r = wce::plan_route(route_facts(c, in, out, mask));
+    const wce::Route r = wce::plan_route(route_facts(c, in, out, mask, ow2 != nullptr));
     const wce::LsArgs la = ls_args(in, out, mask, eq_src);
     if (r.ls_pass) {
         rc = wce::launch_ls(c->d_state, la, stream);
@@ -625,6 +634,7 @@ static int estimate_impl(wce_ctx *c, const wce_frames *in, const wce_outputs *ou
     }
     if (!(mask & WCE_EST_PS_MMSE)) return WCE_OK;
     wce::SolveArgs sa = solve_args(c, in, out->ps_mmse, out->out_stride);
+    sa.ow2 = ow2;
     const bool split = sa.nblk > 1;   // MATLAB: one wave per (frame, block), averaged after
     if (split && n * sa.nblk > INT32_MAX) return fail(WCE_EINVAL, "n_frames * 4 > 2^31 - 1 (MATLAB semantics)");
     std::unique_lock<std::mutex> lk;
@@ -704,6 +714,12 @@ static int estimate_impl(wce_ctx *c, const wce_frames *in, const wce_outputs *ou
 int wce_estimate(wce_ctx *c, const wce_frames *in, const wce_outputs *out, uint32_t mask, void *stream)
 {
     return estimate_impl(c, in, out, mask, stream, nullptr);
+}
+
+int wce_estimate_noise(wce_ctx *c, const wce_frames *in, const wce_outputs *out, uint32_t mask, const double *ow2,
+                       void *stream)
+{
+    return estimate_impl(c, in, out, mask, stream, nullptr, ow2);
 }
 
 struct wce_plan {

@@ -182,6 +182,8 @@ struct SolveArgs {
     int32_t mmse_done;        // ref_ls_elem_kernel only, set by launch_ref_ls_elem: H already written (REF
                               // frame covariance), the launch runs the LS family only
     const uint8_t *skip;      // per unit: nonzero = H already written (constant-modulus path); null = none
+    const double *ow2;        // wce_estimate_noise: ow2[f] replaces State::bcoef in frame f's solve; null = State::bcoef.
+                              // mmse_rank1_kernel only: every other launcher that takes SolveArgs refuses it
 };
 struct SynthArgs {
     double *tx, *rx, *rx_pre;
@@ -209,7 +211,8 @@ int launch_mmse_ref_pilots(const State *st, const SolveArgs &a, void *stream);
 // the 53 x 53 factorisation: Bordered mmse_solve_fc_kernel, Rank1Build mmse_solve_kernel<true>,
 // Dense mmse_solve_kernel<false>
 int launch_mmse_factor(const State *st, const SolveArgs &a, SolveForm form, void *stream);
-// the closed-form bordered rank-1 solve (wce_rank1.hip); nt: nontemporal loads and stores
+// the closed-form bordered rank-1 solve (wce_rank1.hip); nt: nontemporal loads and stores;
+// a.ow2 set: its per-frame-noise build
 int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, void *stream);
 // the same factorisation + LS family + equalization of each frame in one launch (C semantics, one block)
 int launch_mmse_solve_ls(const State *st, const SolveArgs &a, const LsArgs &l, SolveForm form, void *stream);

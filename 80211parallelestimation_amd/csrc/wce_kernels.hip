@@ -3090,6 +3090,7 @@ int launch_ls(const State *st, const LsArgs &a, void *stream)
 
 int launch_mmse_ref_pilots(const State *st, const SolveArgs &a, void *stream)
 {
+    if (a.ow2) return WCE_EINVAL;   // per-frame noise runs on mmse_rank1_kernel only (wce_route.h)
     if (a.n <= 0) return WCE_OK;
     if (a.n > 0x7fffffffll) return WCE_EINVAL;
     if (!a.cu || a.split || a.nblk > 1) return WCE_EINVAL;   // block averaging runs split, on the factorisation
@@ -3115,6 +3116,7 @@ int launch_mmse_ref_pilots(const State *st, const SolveArgs &a, void *stream)
 
 int launch_mmse_factor(const State *st, const SolveArgs &a, SolveForm form, void *stream)
 {
+    if (a.ow2) return WCE_EINVAL;   // per-frame noise runs on mmse_rank1_kernel only (wce_route.h)
     if (a.n <= 0) return WCE_OK;
     const int64_t waves = a.split ? a.n * a.nblk : a.n;
     if (waves > 0x7fffffffll) return WCE_EINVAL;
@@ -3204,6 +3206,7 @@ const char *lr_kernel_name(int k0, int rank, int taps, int64_t units)
 
 int launch_mmse_lr(const State *st, int k0, int rank, int taps, const SolveArgs &a, void *stream)
 {
+    if (a.ow2) return WCE_EINVAL;   // per-frame noise runs on mmse_rank1_kernel only (wce_route.h)
     if (a.n <= 0) return WCE_OK;
     const int64_t waves = a.split ? a.n * a.nblk : a.n;
     if (waves > 0x7fffffffll) return WCE_EINVAL;
@@ -3297,6 +3300,7 @@ int launch_fc_finish(const SolveArgs &a, const double *dots, double *H, int64_t 
 
 int launch_ref_ls_elem(const State *st, const SolveArgs &a, const LsArgs &l, bool mmse_done, void *stream)
 {
+    if (a.ow2) return WCE_EINVAL;   // per-frame noise runs on mmse_rank1_kernel only (wce_route.h)
     if (a.n <= 0) return WCE_OK;
     if (!a.cu || a.split || a.nblk > 1) return WCE_EINVAL;
     SolveArgs am = a;
@@ -3314,6 +3318,7 @@ int launch_ref_ls_elem(const State *st, const SolveArgs &a, const LsArgs &l, boo
 
 int launch_mmse_solve_ls(const State *st, const SolveArgs &a, const LsArgs &l, SolveForm form, void *stream)
 {
+    if (a.ow2) return WCE_EINVAL;   // per-frame noise runs on mmse_rank1_kernel only (wce_route.h)
     if (a.n <= 0) return WCE_OK;
     if (a.n > 0x7fffffffll) return WCE_EINVAL;
     if (form != SolveForm::Dense && !a.cu) return WCE_EINVAL;
@@ -3871,6 +3876,7 @@ int launch_matvec(const double *M1, const double *M2, const double *X, int64_t x
 int launch_ref_fc(const State *st, const SolveArgs &a, const double *rx_pre, int64_t ps, const double *tx_pre,
                   void *stream)
 {
+    if (a.ow2) return WCE_EINVAL;   // per-frame noise runs on mmse_rank1_kernel only (wce_route.h)
     if (a.n <= 0) return WCE_OK;
     if (a.split || !rx_pre || !a.w) return WCE_EINVAL;
     const int64_t blocks = tile_blocks((a.n + 15) / 16, APPLY_WAVES * FC_WG_PER_CU);
@@ -3904,6 +3910,7 @@ int launch_ref_w(const State *st, const double *X, int64_t xs, double *W, int64_
 
 int launch_cm(const State *st, const SolveArgs &a, uint8_t *flags, void *stream)
 {
+    if (a.ow2) return WCE_EINVAL;   // per-frame noise runs on mmse_rank1_kernel only (wce_route.h)
     if (a.n <= 0) return WCE_OK;
     if (a.split || !flags) return WCE_EINVAL;
     const int64_t blocks = (a.n + 16 * APPLY_WAVES - 1) / (16 * APPLY_WAVES);

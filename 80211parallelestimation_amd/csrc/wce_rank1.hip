@@ -90,7 +90,12 @@ __device__ __forceinline__ double2 rank1_s(const double2 (&x)[4], const double2 
 // One 16-lane row per unit g = frame (or, split, frame * nblk + block): H = u s
 // to row f of a.w, or (split, MATLAB averaging) s_b to a.dots[g] for
 // fc_finish_kernel.  NT: nontemporal tx / rx loads and H stores (A/B).
-template <bool NT>
+// NOISE (wce_estimate_noise): b = a.ow2[f], the frame's own noise variance (TEXTBOOK's b is
+// ow2 itself), one 8-byte load per lane at the row's common address, issued with the other
+// 16.  A frame whose ow2 is not positive and finite gets s = NaN through the same stores
+// (split: a NaN dot, so fc_finish_kernel's mean is NaN): its row is all NaN, and no address
+// depends on the value.  The build without NOISE never reads a.ow2.
+template <bool NT, bool NOISE>
 __global__ __launch_bounds__(256) void mmse_rank1_kernel(const State *__restrict__ st, SolveArgs a)
 {
     const int i = threadIdx.x & 15;
@@ -102,7 +107,7 @@ __global__ __launch_bounds__(256) void mmse_rank1_kernel(const State *__restrict
     const int64_t base = f * a.fs + (int64_t)(a.blk + b) * a.bs;
     const int64_t cb = f * a.cs;
     const bool cwg = a.cw != nullptr;
-    const double ac = st->acoef, bc = st->bcoef;
+    const double ac = st->acoef, bc = NOISE ? a.ow2[f] : st->bcoef;
     const uint64_t xm = st->xmask;
     const double2 zero = make_double2(0.0, 0.0);
     double2 x[4], r[4], u[4], w[4];
@@ -120,7 +125,8 @@ __global__ __launch_bounds__(256) void mmse_rank1_kernel(const State *__restrict
         u[m] = live ? ul : zero;
         w[m] = live ? wl : zero;
     }
-    const double2 s = rank1_s(x, r, u, w, cwg, ac, bc);
+    double2 s = rank1_s(x, r, u, w, cwg, ac, bc);
+    if (NOISE && !(bc > 0.0 && bc < __builtin_inf())) s = make_double2(__builtin_nan(""), __builtin_nan(""));
     if (a.split) {
         if (i == 0) st2(a.dots, g, s);
         return;
@@ -145,8 +151,16 @@ int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, void *stream
     const int64_t units = a.split ? a.n * a.nblk : a.n;
     if (units > 0x7fffffffll) return WCE_EINVAL;
     const dim3 g((unsigned)((units + 15) / 16)), b(256);
-    if (nt) hipLaunchKernelGGL(mmse_rank1_kernel<true>, g, b, 0, (hipStream_t)stream, st, a);
-    else hipLaunchKernelGGL(mmse_rank1_kernel<false>, g, b, 0, (hipStream_t)stream, st, a);
+    hipStream_t s = (hipStream_t)stream;
+    if (a.ow2) {   // per-frame noise: TEXTBOOK only (check_route_facts), so w = conj(u)
+        if (a.cw) return WCE_EINVAL;
+        if (nt) hipLaunchKernelGGL((mmse_rank1_kernel<true, true>), g, b, 0, s, st, a);
+        else hipLaunchKernelGGL((mmse_rank1_kernel<false, true>), g, b, 0, s, st, a);
+    } else if (nt) {
+        hipLaunchKernelGGL((mmse_rank1_kernel<true, false>), g, b, 0, s, st, a);
+    } else {
+        hipLaunchKernelGGL((mmse_rank1_kernel<false, false>), g, b, 0, s, st, a);
+    }
     return hipGetLastError() == hipSuccess ? WCE_OK : WCE_EHIP;
 }
 

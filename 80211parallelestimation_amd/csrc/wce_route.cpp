@@ -16,6 +16,8 @@ int check_route_facts(const RouteFacts &f)
     if (f.mask & ~0x7Fu) return WCE_EINVAL;
     if ((f.mask & WCE_MMSE_FRAME_COV) && !(f.mask & WCE_EST_PS_MMSE)) return WCE_EINVAL;
     if (f.mode != WCE_MMSE_COV && (f.lr_k0 >= 0 || f.cm)) return WCE_EINVAL;   // no such context
+    // per-frame ow2 is the .m model's: b = ow2 enters the TEXTBOOK closed form only
+    if (f.noise && (f.mode != WCE_MMSE_TEXTBOOK || !(f.mask & WCE_EST_PS_MMSE))) return WCE_EINVAL;
     return WCE_OK;
 }
 
@@ -37,11 +39,13 @@ Route plan_route(const RouteFacts &f)
     // the second bordered row gives H = cu (cw . W) without the apply step.
     const bool pilots = f.mode == WCE_MMSE_REF && f.bdot;
     const bool rank1 = fc || pilots || f.mode == WCE_MMSE_TEXTBOOK;
-    const bool bordered = fc || pilots || (f.mode == WCE_MMSE_TEXTBOOK && f.bdot);
+    const bool bordered = fc || pilots || (f.mode == WCE_MMSE_TEXTBOOK && (f.bdot || f.noise));
     // A bordered rank-1 solve off REF's pilot form has a closed form bound by the frames' HBM
     // traffic: no VALU-bound solve is left for the LS traffic to hide under, so such a request
-    // runs the LS pass, then that kernel.  Variant R1 = 1 keeps the factorisation.
-    const bool closed = bordered && !pilots && f.r1 != 1;
+    // runs the LS pass, then that kernel.  Variant R1 = 1 keeps the factorisation -- except with
+    // per-frame noise (TEXTBOOK only, check_route_facts): the factorising kernels read State::bcoef,
+    // so that request takes the closed form whatever the border dot and R1 knobs say.
+    const bool closed = bordered && !pilots && (f.r1 != 1 || f.noise);
     // Config-5 fusion: the LS family and equalization ride in the solve's epilogue (C semantics)
     const bool fuse = f.fuse && ls && mmse && c_sem && lr_k0 < 0 && !r.cm && !closed;
     r.ls_pass = ls && !fuse;
@@ -125,6 +129,16 @@ extern "C" int wce_debug_route(int mode, int bdot, int fuse, int cm, int lr_k0, 
                                unsigned mask, int ls_f32, int r1, int ref_fc, int ref_ls, char *buf, size_t cap)
 {
     const wce::RouteFacts f{mode, bdot != 0, fuse != 0, cm != 0, lr_k0, cov_rank, semantics, mask, ls_f32 != 0, r1, ref_fc, ref_ls};
+    if (wce::check_route_facts(f)) return WCE_EINVAL;
+    return wce::route_names(wce::plan_route(f), buf, cap) < 0 ? WCE_EINVAL : WCE_OK;
+}
+
+extern "C" int wce_debug_route_noise(int mode, int bdot, int fuse, int cm, int lr_k0, int cov_rank, int semantics,
+                                     unsigned mask, int ls_f32, int r1, int ref_fc, int ref_ls, int noise, char *buf,
+                                     size_t cap)
+{
+    wce::RouteFacts f{mode, bdot != 0, fuse != 0, cm != 0, lr_k0, cov_rank, semantics, mask, ls_f32 != 0, r1, ref_fc, ref_ls};
+    f.noise = noise != 0;
     if (wce::check_route_facts(f)) return WCE_EINVAL;
     return wce::route_names(wce::plan_route(f), buf, cap) < 0 ? WCE_EINVAL : WCE_OK;
 }

@@ -24,6 +24,7 @@ struct RouteFacts {
     uint32_t mask;     // estimator bits of the request
     bool ls_f32;       // WCE_OUT_LS_F32
     int r1, ref_fc, ref_ls;   // WCE_VARIANT_R1 / REF_FC / REF_LS, read once by the caller
+    bool noise;        // wce_estimate_noise: each frame's own ow2 (TEXTBOOK + PS_MMSE; always the closed form)
 };
 
 // WCE_MMSE_FRAME_COV: how the per-frame factors u_f (and w_f) come about

@@ -103,6 +103,7 @@ ABI = {
     "wce_debug_set_cov_path": [c_void_p, c_int],
     "wce_debug_lr_kernel": [c_void_p, c_int64],
     "wce_debug_route": [c_int] * 7 + [c_uint32] + [c_int] * 4 + [ctypes.c_char_p, c_size_t],
+    "wce_debug_route_noise": [c_int] * 7 + [c_uint32] + [c_int] * 5 + [ctypes.c_char_p, c_size_t],
     "wce_debug_cov_factor": [c_void_p, c_size_t, c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_double),
                              POINTER(c_double)],
     "wce_ctx_cov_info": [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_double), POINTER(c_double)],
@@ -118,6 +119,7 @@ ABI = {
     "wce_state_validate": [c_void_p, c_size_t, POINTER(c_int)],
     "wce_ctx_get_shared": [c_void_p, c_void_p, c_void_p, POINTER(c_double), POINTER(c_double)],
     "wce_estimate": [c_void_p, POINTER(Frames), POINTER(Outputs), c_uint32, c_void_p],
+    "wce_estimate_noise": [c_void_p, POINTER(Frames), POINTER(Outputs), c_uint32, c_void_p, c_void_p],
     "wce_mmse_solve": [c_void_p, POINTER(Frames), c_void_p, c_int64, c_void_p],
     "wce_mmse_apply": [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p],
     "wce_synth_frames": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64,
@@ -427,8 +429,14 @@ class Context:
             _check(_lib.wce_stream_synchronize(stream), "wce_stream_synchronize")
         return bitmap.numpy(), int(n_bad.numpy()[0])
 
-    def estimate(self, frames: Frames, outputs: Outputs, mask: int, stream=None):
-        _check(_lib.wce_estimate(self.handle, byref(frames), byref(outputs), mask, stream), "wce_estimate")
+    def estimate(self, frames: Frames, outputs: Outputs, mask: int, stream=None, ow2=None):
+        """wce_estimate; ow2 (a device array of n_frames doubles, e.g. front_end_preamble's): wce_estimate_noise,
+        each frame's PS_MMSE with its own noise variance (TEXTBOOK contexts)."""
+        if ow2 is None:
+            _check(_lib.wce_estimate(self.handle, byref(frames), byref(outputs), mask, stream), "wce_estimate")
+            return
+        _check(_lib.wce_estimate_noise(self.handle, byref(frames), byref(outputs), mask, _addr(ow2), stream),
+               "wce_estimate_noise")
 
     def mmse_solve(self, frames: Frames, W, w_stride=NSC, stream=None):
         _check(_lib.wce_mmse_solve(self.handle, byref(frames), _addr(W), w_stride, stream), "wce_mmse_solve")
@@ -478,14 +486,27 @@ class Context:
         return sym, pre, ow2
 
     def estimate_host(self, tx, rx, rx_pre=None, mask=ALL, block=0, eq_source=PS_LINEAR, semantics=SEM_C,
-                      tx_pre=None, ls_f32=False):
-        """Convenience: host numpy frames [B][15][53] -> dict of host outputs."""
+                      tx_pre=None, ls_f32=False, ow2=None):
+        """Convenience: host numpy frames [B][15][53] -> dict of host outputs.  ow2: host array [B], each
+        frame's own noise variance for PS_MMSE (wce_estimate_noise)."""
         tx, rx = _as_c128(tx), _as_c128(rx)
         B = tx.shape[0]
         if tx.shape != (B, NBLK, NSC) or rx.shape != tx.shape:
             raise ValueError("tx/rx must be [B][15][53] complex")
         dtx, drx = DeviceArray.from_numpy(tx), DeviceArray.from_numpy(rx)
         dpre = DeviceArray.from_numpy(_as_c128(rx_pre)) if rx_pre is not None else None
+        dow2 = None
+        if ow2 is not None:
+            ow2 = np.ascontiguousarray(np.asarray(ow2, dtype=np.float64))
+            if ow2.shape != (B,):
+                raise ValueError("ow2 must be [B] float")
+            dow2 = DeviceArray.from_numpy(ow2)
+        dtp = DeviceArray.from_numpy(_as_c128(tx_pre)) if tx_pre is not None else None
+        return self._estimate_device(dtx, drx, dpre, B, mask, block, eq_source, semantics, dtp, ls_f32, dow2)
+
+    def _estimate_device(self, dtx, drx, dpre, B, mask, block, eq_source, semantics, dtp, ls_f32, dow2):
+        """estimate_host's device half: dense [B][15][53] frames (and rx_pre [B][53], tx_pre [53], ow2 [B] or
+        None) on the device -> dict of host outputs"""
         names = [("lt_ls", LT_LS), ("ps_linear", PS_LINEAR), ("ps_cubic", PS_CUBIC), ("ps_sinc", PS_SINC),
                  ("ps_mmse", PS_MMSE)]
         lsdt = np.complex64 if ls_f32 else np.complex128
@@ -495,13 +516,42 @@ class Context:
         o = Outputs(*[(outs[n].addr if n in outs else None) for n, _ in names],
                     deq.addr if deq is not None else None, NSC, NBLK * NSC, NSC, eq_source,
                     OUT_LS_F32 if ls_f32 else 0)
-        dtp = DeviceArray.from_numpy(_as_c128(tx_pre)) if tx_pre is not None else None
         fr = self.frames(dtx, drx, B, rx_pre=dpre, block=block, semantics=semantics, tx_pre=dtp)
-        self.estimate(fr, o, mask)
+        self.estimate(fr, o, mask, ow2=dow2)
         synchronize()
         res = {n: outs[n].numpy() for n in outs}
         if deq is not None:
             res["eq"] = deq.numpy()
+        return res
+
+    def receive_host(self, tx_packets, tx_lptot, rx_packets, rx_lptot, mask=ALL, semantics=SEM_MATLAB):
+        """WiFi_RX.m:17-60 for a batch, on the device with no host hop in between: host time-domain packets
+        [B][>= 1200] and long training fields [B][L] of both sides -> the front end (symbols, preamble FFTs and
+        each packet's sigma^2) -> estimate with each frame's own rx preamble (WCE_MMSE_FRAME_COV) and own
+        noise variance (wce_estimate_noise) -> dict of host outputs, plus "ow2" [B].  `mask` must hold PS_MMSE.
+        Needs a WCE_MMSE_TEXTBOOK context built from the shared tx preamble: every packet carries the same
+        tx long training field, and packet 0's FFT is the tx_pre of the call."""
+        pk = [_as_c128(tx_packets), _as_c128(rx_packets)]
+        lp = [_as_c128(tx_lptot), _as_c128(rx_lptot)]
+        B = pk[1].shape[0]
+        if any(p.ndim != 2 or p.shape[0] != B or p.shape[1] < SAMPLES_PER_BLOCK * NBLK for p in pk):
+            raise ValueError("packets must be [B][>= 1200] complex")
+        if any(l.ndim != 2 or l.shape[0] != B for l in lp):
+            raise ValueError("lptot must be [B][L] complex")
+        sym, pre, keep = [], [], []
+        dow2 = DeviceArray((B,), np.float64, zero=True)
+        for side in (0, 1):
+            dp, dl = DeviceArray.from_numpy(pk[side]), DeviceArray.from_numpy(lp[side])
+            keep += [dp, dl]   # read by the queued front end until _estimate_device synchronises
+            dsym, dpre = DeviceArray((B, NBLK, NSC), zero=True), DeviceArray((B, NSC), zero=True)
+            self.front_end_blocks(dp, B, NBLK, dsym, packet_stride=pk[side].shape[1])
+            self.front_end_preamble(dl, B, lp[side].shape[1], dpre, dow2 if side == 1 else None)
+            sym.append(dsym)
+            pre.append(dpre)
+        # same (null) stream throughout: the estimate reads the front end's outputs in order
+        res = self._estimate_device(sym[0], sym[1], pre[1], B, mask | FRAME_COV, 0, PS_LINEAR, semantics, pre[0],
+                                    False, dow2)
+        res["ow2"] = dow2.numpy()
         return res
 
 
@@ -555,12 +605,17 @@ def state_mode(blob: np.ndarray) -> int:
     return m.value
 
 
-def debug_route(mode, bdot, fuse, cm, lr_k0, rank, sem, mask, f32, r1, ref_fc, ref_ls) -> str:
+def debug_route(mode, bdot, fuse, cm, lr_k0, rank, sem, mask, f32, r1, ref_fc, ref_ls, noise=False) -> str:
     """The kernel families one estimate call with these facts launches, in order, ';'-separated
-    (wce_debug_route: the route planner alone, no device); raises WceError for facts validation rejects."""
+    (wce_debug_route: the route planner alone, no device); raises WceError for facts validation rejects.
+    noise: the call carries per-frame ow2 (wce_estimate_noise; wce_debug_route_noise plans it)."""
     buf = ctypes.create_string_buffer(256)
-    _check(load().wce_debug_route(int(mode), int(bdot), int(fuse), int(cm), int(lr_k0), int(rank), int(sem), int(mask),
-                                  int(f32), int(r1), int(ref_fc), int(ref_ls), buf, len(buf)), "wce_debug_route")
+    facts = (int(mode), int(bdot), int(fuse), int(cm), int(lr_k0), int(rank), int(sem), int(mask), int(f32), int(r1),
+             int(ref_fc), int(ref_ls))
+    if noise:
+        _check(load().wce_debug_route_noise(*facts, 1, buf, len(buf)), "wce_debug_route_noise")
+    else:
+        _check(load().wce_debug_route(*facts, buf, len(buf)), "wce_debug_route")
     return buf.value.decode()
 
 

@@ -221,6 +221,31 @@ int wce_ctx_reserve_stream(wce_ctx *ctx, int64_t n_frames, void *stream);
 int wce_estimate(wce_ctx *ctx, const wce_frames *in, const wce_outputs *out,
                  uint32_t mask, void *stream);
 
+/* wce_estimate with each frame's own noise variance: ow2[f] (device, n_frames
+ * doubles, contiguous -- the array wce_front_end_preamble writes) replaces the
+ * context's ow2 in frame f's PS_MMSE, as WiFi_RX.m estimates sigma^2 per packet
+ * (WiFi_RX.m:30) and hands it to WiFi_channel_estimation_PS_MMSE (WiFi_RX.m:57).
+ * ow2 == NULL: exactly wce_estimate.  With ow2 != NULL:
+ *  - Supported: a WCE_MMSE_TEXTBOOK context (the .m model, the only one where
+ *    ow2 is per packet) and WCE_EST_PS_MMSE in `mask`; with or without
+ *    WCE_MMSE_FRAME_COV; WCE_SEM_C and WCE_SEM_MATLAB; any LS-family and
+ *    WCE_EQUALIZE bits alongside (they do not depend on ow2 and run as the LS
+ *    pass, then the closed-form rank-1 solve).  The request always runs that
+ *    closed form, whatever the wce_debug_* A/B knobs say.
+ *  - WCE_EINVAL with a wce_last_error() text, before any launch: a WCE_MMSE_REF
+ *    or WCE_MMSE_COV context; a mask without WCE_EST_PS_MMSE; an ow2 pointer
+ *    that is not 8-byte aligned.
+ *  - The host never reads ow2[] (no synchronisation).  A frame whose ow2[f] is
+ *    not a positive finite number gets every entry of its ps_mmse row set to
+ *    NaN, both parts, so wce_nonfinite_scan flags it; no other frame and no
+ *    other output of that frame is affected.
+ *  - With every ow2[f] equal to the context's ow2, every output is
+ *    bit-identical to wce_estimate on the same request; a frame's bits depend
+ *    on its own data and its own ow2[f] only.
+ * Launch plans (wce_plan_create) keep the context's ow2. */
+int wce_estimate_noise(wce_ctx *ctx, const wce_frames *in, const wce_outputs *out,
+                       uint32_t mask, const double *ow2, void *stream);
+
 /* Launch plans: one wce_estimate call (fixed buffers, strides, mask, batch)
  * captured into a HIP graph once and replayed with a single graph launch --
  * for serving loops that re-run small batches into the same buffers, where

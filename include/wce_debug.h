@@ -77,6 +77,13 @@ int wce_debug_set_variant(int which, int value);
  * WCE_EINVAL for facts wce_estimate's validation rejects, or a short buffer. */
 int wce_debug_route(int mode, int bdot, int fuse, int cm, int lr_k0, int cov_rank, int semantics, unsigned mask,
                     int ls_f32, int r1, int ref_fc, int ref_ls, char *buf, size_t cap);
+/* The same for a wce_estimate_noise call: noise != 0 adds the fact that the
+ * request carries per-frame ow2 (WCE_EINVAL unless the mode is
+ * WCE_MMSE_TEXTBOOK and WCE_EST_PS_MMSE is in the mask; the route is then the
+ * closed form whatever bdot and r1 say).  noise == 0: wce_debug_route. */
+int wce_debug_route_noise(int mode, int bdot, int fuse, int cm, int lr_k0, int cov_rank, int semantics,
+                          unsigned mask, int ls_f32, int r1, int ref_fc, int ref_ls, int noise, char *buf,
+                          size_t cap);
 /* WCE_MMSE_COV solve form for A/B and accuracy probes: 0 = as the state
  * chose (default), 1 = always the dense Ryy solve, 2 = always the low-rank
  * Gram path (at the state's rank).  ctx is a wce_ctx*. */
