@@ -835,9 +835,10 @@ int wce_synth_frames(wce_ctx *c, wce_complex *tx, wce_complex *rx, wce_complex *
 }
 
 // ---------------------------------------------------------------- front end
-int wce_front_end_blocks(wce_ctx *c, const wce_complex *samples, int64_t packet_stride, int64_t n_frames,
-                         int32_t n_blocks, wce_complex *sym, int64_t frame_stride, int64_t block_stride,
-                         void *stream)
+// cfo == null: the plain build (sample_offset is not looked at)
+static int front_blocks(wce_ctx *c, const wce_complex *samples, int64_t packet_stride, int64_t n_frames,
+                        int32_t n_blocks, const double *cfo, int64_t sample_offset, wce_complex *sym,
+                        int64_t frame_stride, int64_t block_stride, void *stream)
 {
     if (!c) return fail(WCE_EINVAL, "null ctx");
     if (n_frames < 0 || n_blocks < 1) return fail(WCE_EINVAL, "n_frames < 0 or n_blocks < 1");
@@ -847,18 +848,43 @@ int wce_front_end_blocks(wce_ctx *c, const wce_complex *samples, int64_t packet_
     if (block_stride < wce::NSC || frame_stride < (int64_t)(n_blocks - 1) * block_stride + wce::NSC)
         return fail(WCE_EINVAL, "output strides too small");
     if (n_frames * n_blocks >= (int64_t)1 << 31) return fail(WCE_EINVAL, "n_frames * n_blocks >= 2^31");
+    if (cfo) {
+        if (reinterpret_cast<uintptr_t>(cfo) % 8) return fail(WCE_EINVAL, "cfo not 8-byte aligned");
+        if (sample_offset >= (int64_t)1 << 31 || sample_offset <= -((int64_t)1 << 31))
+            return fail(WCE_EINVAL, "|sample_offset| >= 2^31");
+    }
     wce::FrontArgs a{};
     a.src = reinterpret_cast<const double *>(samples);
     a.dst = reinterpret_cast<double *>(sym);
     a.ps = packet_stride; a.off = WCE_SAMPLES_PER_BLOCK - WCE_FFT_SIZE; a.fs = frame_stride; a.bs = block_stride;
     a.n_units = (uint32_t)(n_frames * n_blocks); a.nb = (uint32_t)n_blocks;
+    a.cfo = const_cast<double *>(cfo);   // est = 0: read only
+    a.n0 = cfo ? sample_offset + a.off : 0;
     DeviceGuard g(c->device);
     int rc = wce::launch_front(a, false, stream);
     return rc ? fail(rc, "front end launch") : WCE_OK;
 }
 
-int wce_front_end_preamble(wce_ctx *c, const wce_complex *lptot, int64_t lptot_stride, int64_t lptot_len,
-                           int64_t n_frames, wce_complex *pre_fft, int64_t pre_stride, double *ow2, void *stream)
+int wce_front_end_blocks(wce_ctx *c, const wce_complex *samples, int64_t packet_stride, int64_t n_frames,
+                         int32_t n_blocks, wce_complex *sym, int64_t frame_stride, int64_t block_stride,
+                         void *stream)
+{
+    return front_blocks(c, samples, packet_stride, n_frames, n_blocks, nullptr, 0, sym, frame_stride, block_stride,
+                        stream);
+}
+
+int wce_front_end_blocks_cfo(wce_ctx *c, const wce_complex *samples, int64_t packet_stride, int64_t n_frames,
+                             int32_t n_blocks, const double *cfo, int64_t sample_offset, wce_complex *sym,
+                             int64_t frame_stride, int64_t block_stride, void *stream)
+{
+    return front_blocks(c, samples, packet_stride, n_frames, n_blocks, cfo, sample_offset, sym, frame_stride,
+                        block_stride, stream);
+}
+
+// cfo == null: the plain build
+static int front_preamble(wce_ctx *c, const wce_complex *lptot, int64_t lptot_stride, int64_t lptot_len,
+                          int64_t n_frames, wce_complex *pre_fft, int64_t pre_stride, double *ow2, double *cfo,
+                          int estimate, void *stream)
 {
     if (!c) return fail(WCE_EINVAL, "null ctx");
     if (n_frames < 0) return fail(WCE_EINVAL, "n_frames < 0");
@@ -867,15 +893,35 @@ int wce_front_end_preamble(wce_ctx *c, const wce_complex *lptot, int64_t lptot_s
     if (lptot_len < 2 * WCE_FFT_SIZE || lptot_stride < lptot_len) return fail(WCE_EINVAL, "lptot_len < 128 or stride < len");
     if (pre_stride < wce::NSC) return fail(WCE_EINVAL, "pre_stride < 53");
     if (n_frames >= (int64_t)1 << 31) return fail(WCE_EINVAL, "n_frames >= 2^31");
+    if (reinterpret_cast<uintptr_t>(cfo) % 8) return fail(WCE_EINVAL, "cfo not 8-byte aligned");
     wce::FrontArgs a{};
     a.src = reinterpret_cast<const double *>(lptot);
     a.dst = reinterpret_cast<double *>(pre_fft);
     a.ow2 = ow2;
     a.ps = lptot_stride; a.off = lptot_len - 2 * WCE_FFT_SIZE; a.fs = pre_stride; a.bs = 0;
     a.n_units = (uint32_t)n_frames; a.nb = 1;
+    a.cfo = cfo;
+    a.n0 = -2 * WCE_FFT_SIZE;   // the long training field ends at n = 0
+    a.est = cfo && estimate;
     DeviceGuard g(c->device);
     int rc = wce::launch_front(a, true, stream);
     return rc ? fail(rc, "front end launch") : WCE_OK;
+}
+
+int wce_front_end_preamble(wce_ctx *c, const wce_complex *lptot, int64_t lptot_stride, int64_t lptot_len,
+                           int64_t n_frames, wce_complex *pre_fft, int64_t pre_stride, double *ow2, void *stream)
+{
+    return front_preamble(c, lptot, lptot_stride, lptot_len, n_frames, pre_fft, pre_stride, ow2, nullptr, 0, stream);
+}
+
+int wce_front_end_preamble_cfo(wce_ctx *c, const wce_complex *lptot, int64_t lptot_stride, int64_t lptot_len,
+                               int64_t n_frames, wce_complex *pre_fft, int64_t pre_stride, double *ow2, double *cfo,
+                               int estimate, void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    if (!cfo) return fail(WCE_EINVAL, "null cfo");
+    return front_preamble(c, lptot, lptot_stride, lptot_len, n_frames, pre_fft, pre_stride, ow2, cfo, estimate,
+                          stream);
 }
 
 // ---------------------------------------------------------------- runtime helpers

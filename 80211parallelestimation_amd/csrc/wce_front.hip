@@ -100,92 +100,74 @@ __device__ __forceinline__ void dft8(double2 (&x)[8])
     x[3] = cadd(e3, t3); x[7] = csub(e3, t3);
 }
 
-// PRE = false: unit = OFDM block (80 samples, CP 16).  PRE = true: unit =
-// one frame's long training field (two 64-sample copies at a.off, a.off + 64).
-template <bool PRE>
-__global__ __launch_bounds__(256) void front_kernel(FrontArgs a)
+// ---- carrier frequency offset (the CFO builds) ----
+// Sample n (counted from the end of the long training field) is derotated by
+// exp(-2 pi i e n), e = the frame's offset in cycles per sample.  A lane's 8
+// samples sit 8 apart: one base rotor at its first sample, the step rotor
+// exp(-2 pi i 8 e), and products for the other seven -- two sincospi per lane
+// and unit, not one per sample.
+
+// exp(-2 pi i e n).  The phase e n (cycles) is reduced before sincospi sees it:
+// hi + lo = e n exactly, hi - rint(hi) is exact, so the rotor's error does not
+// grow with |e n|.  Contraction is off: fusing e * n into the subtraction would
+// count lo twice.  A non-finite e gives (NaN, NaN).
+__device__ __forceinline__ double2 cfo_rotor(double e, double n)
 {
-    __shared__ double2 lds[FE_WAVES][FE_UNITS][64];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int g = lane >> 3, j = lane & 7;
-    double2 *T = lds[w][g];
-    const double2 *src = reinterpret_cast<const double2 *>(a.src);
-    double2 *dst = reinterpret_cast<double2 *>(a.dst);
-    constexpr bool NT = !PRE, STAGED = !PRE;
-    double2 tw[8];
+#pragma clang fp contract(off)
+    const double hi = e * n, lo = fma(e, n, -hi);
+    const double t = (hi - rint(hi)) + lo;
+    double s, c;
+    sincospi(-2.0 * t, &s, &c);
+    return make_double2(c, s);
+}
+// x[k] *= r0 s^k.  s^2 and s^4 first: no rotor is more than three products from
+// r0.  rot = false (e == 0, every rotor (1, -0)) leaves x as loaded, so that a
+// zero offset keeps the plain build's bits down to the sign of a zero.
+__device__ __forceinline__ void cfo_derotate(double2 (&x)[8], double2 r0, double2 s, bool rot)
+{
+    const double2 s2 = cmul(s, s), s4 = cmul(s2, s2);
+    const double2 r1 = cmul(r0, s);
+    const double2 r[4] = {r0, r1, cmul(r0, s2), cmul(r1, s2)};
 #pragma unroll
-    for (int k1 = 0; k1 < 8; ++k1) tw[k1] = kW64[(j * k1) & 63];
-    const uint32_t stride = gridDim.x * FE_WAVES * FE_UNITS;
-    for (uint32_t u0 = (blockIdx.x * FE_WAVES + w) * FE_UNITS; u0 < a.n_units; u0 += stride) {
-        const bool live = u0 + g < a.n_units;
-        const uint32_t u = live ? u0 + g : a.n_units - 1;
-        const uint32_t f = u / a.nb, b = u - f * a.nb;
-        const double2 *x = src + (int64_t)f * a.ps + a.off + (int64_t)b * 80 + j;
-        double2 v[8];
-        double s2 = 0.0;
-        if constexpr (PRE) {      // WiFi_RX.m:24-30: p2 = x[0..64), p1 = x[64..128)
-            double2 p2[8], p1[8];
-#pragma unroll
-            for (int n1 = 0; n1 < 8; ++n1) { p2[n1] = fe_ld<NT>(x + 8 * n1); p1[n1] = fe_ld<NT>(x + 64 + 8 * n1); }
-#pragma unroll
-            for (int n1 = 0; n1 < 8; ++n1) {
-                v[n1] = cscale(cadd(p1[n1], p2[n1]), 0.5);
-                const double2 d = csub(p2[n1], p1[n1]);
-                s2 += d.x * d.x + d.y * d.y;
-            }
-        } else {
-#pragma unroll
-            for (int n1 = 0; n1 < 8; ++n1) v[n1] = fe_ld<NT>(x + 8 * n1);
-        }
-        // stage 1 (lane = n2): DFT over n1, then W64^(n2 k1)
-        dft8(v);
-#pragma unroll
-        for (int k1 = 1; k1 < 8; ++k1) v[k1] = cmul(v[k1], tw[k1]);
-        // transpose: element (n2, k1) at n2 * 8 + (k1 ^ n2)
-#pragma unroll
-        for (int k1 = 0; k1 < 8; ++k1) T[j * 8 + (k1 ^ j)] = v[k1];
-        wave_lds_sync();
-#pragma unroll
-        for (int n2 = 0; n2 < 8; ++n2) v[n2] = T[n2 * 8 + (j ^ n2)];
-        wave_lds_sync();
-        // stage 2 (lane = k1): DFT over n2 -> bin k = k1 + 8 k2
-        dft8(v);
-        if constexpr (STAGED) {
-            // stage the 8 x 53 bins in LDS, then store them as one run per wave
-            // (contiguous when consecutive blocks are adjacent, block_stride 53)
-#pragma unroll
-            for (int k2 = 0; k2 < 8; ++k2) T[(j + 8 * k2 + 26) & 63] = v[k2];
-            wave_lds_sync();
-#pragma unroll
-            for (int t = 0; t < (FE_UNITS * NSC + 63) / 64; ++t) {
-                const int e = lane + 64 * t;
-                const int ug = e / NSC, i = e - ug * NSC;
-                const uint32_t uu = u0 + ug;
-                if (e < FE_UNITS * NSC && uu < a.n_units) {
-                    const uint32_t ff = uu / a.nb, bb = uu - ff * a.nb;
-                    fe_st<NT>(dst + (int64_t)ff * a.fs + (int64_t)bb * a.bs + i, lds[w][ug][i]);
-                }
-            }
-            wave_lds_sync();
-        } else {
-            double2 *y = dst + (int64_t)f * a.fs + (int64_t)b * a.bs;
-#pragma unroll
-            for (int k2 = 0; k2 < 8; ++k2) {
-                const int i = (j + 8 * k2 + 26) & 63;   // circshift(., 26), keep 1:53
-                if (live && i < NSC) fe_st<NT>(y + i, v[k2]);
-            }
-        }
-        if constexpr (PRE) {
-            if (a.ow2) {
-                s2 += __shfl_xor(s2, 1, 64);
-                s2 += __shfl_xor(s2, 2, 64);
-                s2 += __shfl_xor(s2, 4, 64);
-                if (live && j == 0) a.ow2[f] = s2 / 128.0;   // 2 K, K = 64
-            }
-        }
+    for (int k = 0; k < 4; ++k) {
+        const double2 a = x[k], b = x[k + 4];
+        const double2 lo = cmul(a, r[k]), hi = cmul(b, cmul(r[k], s4));
+        x[k] = make_double2(rot ? lo.x : a.x, rot ? lo.y : a.y);
+        x[k + 4] = make_double2(rot ? hi.x : b.x, rot ? hi.y : b.y);
     }
 }
 
+// v tw with the roundings spelled out: a.y b.y and a.x b.y round, the other two products fuse.  These
+// are the plain builds' roundings; left to contraction, the compiler picks per build which product of
+// each pair to fuse, and a CFO build given a zero offset would part from the plain build's bits.
+__device__ __forceinline__ double2 cmul_tw(double2 a, double2 b)
+{
+#pragma clang fp contract(off)
+    return make_double2(fma(a.x, b.x, -(a.y * b.y)), fma(a.y, b.x, a.x * b.y));
+}
+
+// PRE = false: unit = OFDM block (80 samples, CP 16).  PRE = true: unit =
+// one frame's long training field (two 64-sample copies at a.off, a.off + 64).
+// The kernels' one body is wce_front_body.h, included into each kernel as it
+// stands: the plain builds compile to the code they had before the CFO builds
+// existed (as a function shared by both, the body is simplified before it is
+// inlined, and the plain builds come out differently scheduled and, in one
+// twiddle product, differently rounded).
+template <bool PRE>
+__global__ __launch_bounds__(256) void front_kernel(FrontArgs a)
+{
+    constexpr bool CFO = false;
+#include "wce_front_body.h"
+}
+// CFO: derotate the samples first (a.cfo, a.n0, a.est).
+template <bool PRE>
+__global__ __launch_bounds__(256) void front_cfo_kernel(FrontArgs a)
+{
+    constexpr bool CFO = true;
+#include "wce_front_body.h"
+}
+
+// a.cfo != null: the CFO builds
 int launch_front(const FrontArgs &a, bool preamble, void *stream)
 {
     if (a.n_units == 0) return 0;
@@ -193,7 +175,11 @@ int launch_front(const FrontArgs &a, bool preamble, void *stream)
     uint32_t blocks = (a.n_units + units_per_wg - 1) / units_per_wg;
     if (blocks > 256u * 40u) blocks = 256u * 40u;   // grid-stride beyond ~40 workgroups per CU
     const dim3 grid(blocks), blk(256);
-    if (preamble)
+    if (a.cfo && preamble)
+        hipLaunchKernelGGL(front_cfo_kernel<true>, grid, blk, 0, (hipStream_t)stream, a);
+    else if (a.cfo)
+        hipLaunchKernelGGL(front_cfo_kernel<false>, grid, blk, 0, (hipStream_t)stream, a);
+    else if (preamble)
         hipLaunchKernelGGL(front_kernel<true>, grid, blk, 0, (hipStream_t)stream, a);
     else
         hipLaunchKernelGGL(front_kernel<false>, grid, blk, 0, (hipStream_t)stream, a);
@@ -201,3 +187,4 @@ int launch_front(const FrontArgs &a, bool preamble, void *stream)
 }
 
 }  // namespace wce
+

@@ -201,6 +201,11 @@ struct FrontArgs {
     double *ow2;          // preamble only, may be null
     int64_t ps, off, fs, bs;
     uint32_t n_units, nb;
+    // carrier frequency offset (null cfo: the plain builds, nothing below is read): frame f's samples are
+    // derotated by exp(-2 pi i cfo[f] n); the unit's first sample (src[... + off + 80*b]) is at n = n0 + 80*b
+    double *cfo;          // [n_frames] cycles per sample; read, or written by the preamble build when est
+    int64_t n0;
+    int32_t est;          // preamble only: cfo[f] = the two-copy estimate of frame f
 };
 
 int launch_ls(const State *st, const LsArgs &a, void *stream);

@@ -127,6 +127,10 @@ ABI = {
     "wce_front_end_blocks": [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_int64, c_void_p],
     "wce_front_end_preamble": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p,
                                c_void_p],
+    "wce_front_end_blocks_cfo": [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64,
+                                 c_int64, c_void_p],
+    "wce_front_end_preamble_cfo": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p,
+                                   c_void_p, c_int, c_void_p],
     "wce_nonfinite_scan": [c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int64, c_uint32, c_void_p, c_void_p,
                            c_void_p],
     "wce_comm_unique_id": [c_void_p],
@@ -451,39 +455,60 @@ class Context:
                                      stream), "wce_synth_frames")
 
     def front_end_blocks(self, samples, n_frames, n_blocks=NBLK, sym=None, packet_stride=None,
-                         frame_stride=NBLK * NSC, block_stride=NSC, stream=None):
-        """Time-domain packets (device) -> 53-bin OFDM symbols (WiFi_blocks_extraction.m)."""
+                         frame_stride=NBLK * NSC, block_stride=NSC, stream=None, cfo=None, sample_offset=0):
+        """Time-domain packets (device) -> 53-bin OFDM symbols (WiFi_blocks_extraction.m).  cfo (a device
+        array of n_frames doubles, cycles per sample, e.g. front_end_preamble's): wce_front_end_blocks_cfo,
+        packet sample m derotated as sample m + sample_offset after the end of the long training field."""
         ps = packet_stride if packet_stride is not None else SAMPLES_PER_BLOCK * n_blocks
-        _check(_lib.wce_front_end_blocks(self.handle, _addr(samples), ps, n_frames, n_blocks, _addr(sym),
-                                         frame_stride, block_stride, stream), "wce_front_end_blocks")
+        if cfo is None:
+            _check(_lib.wce_front_end_blocks(self.handle, _addr(samples), ps, n_frames, n_blocks, _addr(sym),
+                                             frame_stride, block_stride, stream), "wce_front_end_blocks")
+            return
+        _check(_lib.wce_front_end_blocks_cfo(self.handle, _addr(samples), ps, n_frames, n_blocks, _addr(cfo),
+                                             sample_offset, _addr(sym), frame_stride, block_stride, stream),
+               "wce_front_end_blocks_cfo")
 
     def front_end_preamble(self, lptot, n_frames, lptot_len, pre_fft, ow2=None, lptot_stride=None,
-                           pre_stride=NSC, stream=None):
-        """Long training fields (device) -> preamble FFT [53] and sigma^2 per frame (WiFi_RX.m:18-30)."""
+                           pre_stride=NSC, stream=None, cfo=None, estimate_cfo=True):
+        """Long training fields (device) -> preamble FFT [53] and sigma^2 per frame (WiFi_RX.m:18-30).  cfo (a
+        device array of n_frames doubles): wce_front_end_preamble_cfo, which writes each frame's two-copy
+        estimate there (estimate_cfo) or reads it, and derotates the field before anything else."""
         ls = lptot_stride if lptot_stride is not None else lptot_len
-        _check(_lib.wce_front_end_preamble(self.handle, _addr(lptot), ls, lptot_len, n_frames, _addr(pre_fft),
-                                           pre_stride, _addr(ow2), stream), "wce_front_end_preamble")
+        if cfo is None:
+            _check(_lib.wce_front_end_preamble(self.handle, _addr(lptot), ls, lptot_len, n_frames, _addr(pre_fft),
+                                               pre_stride, _addr(ow2), stream), "wce_front_end_preamble")
+            return
+        _check(_lib.wce_front_end_preamble_cfo(self.handle, _addr(lptot), ls, lptot_len, n_frames, _addr(pre_fft),
+                                               pre_stride, _addr(ow2), _addr(cfo), 1 if estimate_cfo else 0, stream),
+               "wce_front_end_preamble_cfo")
 
-    def front_end_host(self, packets, lptot=None, n_blocks=NBLK):
+    def front_end_host(self, packets, lptot=None, n_blocks=NBLK, cfo=False, sample_offset=0):
         """Convenience: host packets [B][80 n_blocks] (+ lptot [B][L]) -> (sym [B][n_blocks][53],
-        pre_fft [B][53] or None, ow2 [B] or None)."""
+        pre_fft [B][53] or None, ow2 [B] or None).  cfo: each packet's carrier frequency offset is estimated
+        from its lptot and removed from both (the packet starts sample_offset samples after the field); a
+        fourth value, cfo [B] in cycles per sample, is returned."""
         packets = _as_c128(packets)
         B = packets.shape[0]
+        if cfo and lptot is None:
+            raise ValueError("cfo needs lptot")
         dp = DeviceArray.from_numpy(packets)
         dsym = DeviceArray((B, n_blocks, NSC), zero=True)
-        self.front_end_blocks(dp, B, n_blocks, dsym, packet_stride=packets.shape[1], frame_stride=n_blocks * NSC)
+        dcfo = DeviceArray((B,), np.float64, zero=True) if cfo else None
         pre = ow2 = None
         if lptot is not None:
             lptot = _as_c128(lptot)
             dl = DeviceArray.from_numpy(lptot)
             dpre = DeviceArray((B, NSC), zero=True)
             dow2 = DeviceArray((B,), np.float64, zero=True)
-            self.front_end_preamble(dl, B, lptot.shape[1], dpre, dow2)
+            self.front_end_preamble(dl, B, lptot.shape[1], dpre, dow2, cfo=dcfo)
+        # after the preamble on the same (null) stream: its estimate is the blocks' cfo
+        self.front_end_blocks(dp, B, n_blocks, dsym, packet_stride=packets.shape[1], frame_stride=n_blocks * NSC,
+                              cfo=dcfo, sample_offset=sample_offset)
         synchronize()
         sym = dsym.numpy()
         if lptot is not None:
             pre, ow2 = dpre.numpy(), dow2.numpy()
-        return sym, pre, ow2
+        return (sym, pre, ow2, dcfo.numpy()) if cfo else (sym, pre, ow2)
 
     def estimate_host(self, tx, rx, rx_pre=None, mask=ALL, block=0, eq_source=PS_LINEAR, semantics=SEM_C,
                       tx_pre=None, ls_f32=False, ow2=None):
@@ -524,13 +549,18 @@ class Context:
             res["eq"] = deq.numpy()
         return res
 
-    def receive_host(self, tx_packets, tx_lptot, rx_packets, rx_lptot, mask=ALL, semantics=SEM_MATLAB):
+    def receive_host(self, tx_packets, tx_lptot, rx_packets, rx_lptot, mask=ALL, semantics=SEM_MATLAB, cfo=False,
+                     sample_offset=0):
         """WiFi_RX.m:17-60 for a batch, on the device with no host hop in between: host time-domain packets
         [B][>= 1200] and long training fields [B][L] of both sides -> the front end (symbols, preamble FFTs and
         each packet's sigma^2) -> estimate with each frame's own rx preamble (WCE_MMSE_FRAME_COV) and own
         noise variance (wce_estimate_noise) -> dict of host outputs, plus "ow2" [B].  `mask` must hold PS_MMSE.
         Needs a WCE_MMSE_TEXTBOOK context built from the shared tx preamble: every packet carries the same
-        tx long training field, and packet 0's FFT is the tx_pre of the call."""
+        tx long training field, and packet 0's FFT is the tx_pre of the call.
+        cfo: each received packet's carrier frequency offset is estimated from its long training field and
+        removed from the field and the packet (which starts sample_offset samples after the field) before
+        anything else, on the same stream; the dict gains "cfo" [B], cycles per sample.  The tx side is the
+        clean reference and is never derotated."""
         pk = [_as_c128(tx_packets), _as_c128(rx_packets)]
         lp = [_as_c128(tx_lptot), _as_c128(rx_lptot)]
         B = pk[1].shape[0]
@@ -540,18 +570,26 @@ class Context:
             raise ValueError("lptot must be [B][L] complex")
         sym, pre, keep = [], [], []
         dow2 = DeviceArray((B,), np.float64, zero=True)
+        dcfo = DeviceArray((B,), np.float64, zero=True) if cfo else None
         for side in (0, 1):
             dp, dl = DeviceArray.from_numpy(pk[side]), DeviceArray.from_numpy(lp[side])
             keep += [dp, dl]   # read by the queued front end until _estimate_device synchronises
             dsym, dpre = DeviceArray((B, NBLK, NSC), zero=True), DeviceArray((B, NSC), zero=True)
-            self.front_end_blocks(dp, B, NBLK, dsym, packet_stride=pk[side].shape[1])
-            self.front_end_preamble(dl, B, lp[side].shape[1], dpre, dow2 if side == 1 else None)
+            if side == 1 and cfo:   # the preamble's estimate first: the blocks read it
+                self.front_end_preamble(dl, B, lp[side].shape[1], dpre, dow2, cfo=dcfo)
+                self.front_end_blocks(dp, B, NBLK, dsym, packet_stride=pk[side].shape[1], cfo=dcfo,
+                                      sample_offset=sample_offset)
+            else:
+                self.front_end_blocks(dp, B, NBLK, dsym, packet_stride=pk[side].shape[1])
+                self.front_end_preamble(dl, B, lp[side].shape[1], dpre, dow2 if side == 1 else None)
             sym.append(dsym)
             pre.append(dpre)
         # same (null) stream throughout: the estimate reads the front end's outputs in order
         res = self._estimate_device(sym[0], sym[1], pre[1], B, mask | FRAME_COV, 0, PS_LINEAR, semantics, pre[0],
                                     False, dow2)
         res["ow2"] = dow2.numpy()
+        if cfo:
+            res["cfo"] = dcfo.numpy()
         return res
 
 

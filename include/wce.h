@@ -304,6 +304,44 @@ int wce_front_end_preamble(wce_ctx *ctx, const wce_complex *lptot, int64_t lptot
                            int64_t n_frames, wce_complex *pre_fft, int64_t pre_stride, double *ow2,
                            void *stream);
 
+/* ---- carrier frequency offset (WiFi_RX.m:4-9 declares one, FO / Fs; no
+ * reference code removes it) ----
+ * cfo[f] (device, n_frames doubles, contiguous, 8-byte aligned) is frame f's
+ * offset in cycles per sample, FO / Fs.  One time axis serves the long training
+ * field and the packet, counted from the end of the field: lptot[i] is sample
+ * n = i - lptot_len, packet sample m is n = m + sample_offset (0: the packet
+ * follows the field directly).  Every sample is derotated in registers,
+ *     y[n] = x[n] exp(-2 pi i cfo[f] n),
+ * before anything else is computed from it; the rest is the plain call.
+ *
+ * wce_front_end_preamble_cfo, estimate != 0: cfo[f] is written, the two-copy
+ * estimate arg(sum_n p1[n] conj(p2[n])) / (2 pi 64) over the 64 sample pairs
+ * of WiFi_RX.m:25-26 (|cfo| < 1/128, +-78 kHz at 10 MHz; an all-zero field
+ * gives 0), and used in the same launch; estimate == 0: cfo[f] is read.  The
+ * mean of the two copies, its DFT and ow2 = sum |p2' - p1'|^2 / 128 are taken
+ * from the derotated copies.  wce_front_end_blocks_cfo reads cfo[f]; cfo ==
+ * NULL: exactly wce_front_end_blocks (sample_offset is ignored).
+ *
+ *  - The host never reads cfo[]; neither call synchronises: the preamble call's
+ *    estimate feeds the blocks call on the same stream with no host hop.
+ *  - WCE_EINVAL (text in wce_last_error()) before any launch: cfo not 8-byte
+ *    aligned; cfo == NULL in the preamble call; |sample_offset| >= 2^31; and
+ *    whatever the plain calls reject.
+ *  - A frame whose given cfo[f] is not finite gets NaN in every bin the call
+ *    writes for it (and in its ow2[f]); a frame whose long training field
+ *    holds a non-finite sample gets NaN in the same bins, in its ow2[f] and,
+ *    when estimated, its cfo[f].  No other frame changes by a bit
+ *    (wce_nonfinite_scan finds such frames).
+ *  - A frame's output bits depend only on its own samples, its cfo[f] and
+ *    sample_offset, not on its place in the batch or the batch's size.
+ *  - A given cfo[f] == 0.0 on finite samples: bit-identical to the plain calls. */
+int wce_front_end_blocks_cfo(wce_ctx *ctx, const wce_complex *samples, int64_t packet_stride, int64_t n_frames,
+                             int32_t n_blocks, const double *cfo, int64_t sample_offset, wce_complex *sym,
+                             int64_t frame_stride, int64_t block_stride, void *stream);
+int wce_front_end_preamble_cfo(wce_ctx *ctx, const wce_complex *lptot, int64_t lptot_stride, int64_t lptot_len,
+                               int64_t n_frames, wce_complex *pre_fft, int64_t pre_stride, double *ow2,
+                               double *cfo, int estimate, void *stream);
+
 /* Non-finite guard.  The reference passes NaN/Inf through
  * silently: main.c's PS_MMSE returns NaN x 53 (main.c:148-212), a zero pilot
  * makes PS_* divide by zero (main.c:82-84), and its dimension checks only
