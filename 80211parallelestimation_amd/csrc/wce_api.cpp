@@ -27,6 +27,7 @@ struct wce_ctx {
     int32_t cov_rank = 0;       // State::cov_rank
     int cov_taps = 0;           // State::cov_taps | State::taps_contig << 1 (diagonal Rhh: the tap-domain forms)
     int cov_path = 0;           // wce_debug_set_cov_path: 0 auto, 1 dense, 2 low-rank
+    int cus = 0;                // CU count of `device`, read once in wce_ctx_create_empty (launch shapes; never on the launch path)
     bool cm_on = false;         // State::cm_on: a constant-modulus operator is loaded (wce_ctx_set_modulus)
     bool cm_use = true;         // wce_debug_set_cm: A/B switch of that path
     std::vector<wce_complex> rhh;   // WCE_MMSE_COV ctx built here: the caller's Rhh (for wce_ctx_set_modulus)
@@ -109,6 +110,10 @@ int wce_ctx_create_empty(wce_ctx **out, int device)
     if (!c) return fail(WCE_ENOMEM, "ctx alloc");
     c->device = device;
     DeviceGuard g(device);
+    if (hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || c->cus <= 0) {
+        delete c;
+        return fail(WCE_EHIP, "hipDeviceGetAttribute(multiprocessor count)");
+    }
     hipError_t e = hipMalloc(&c->d_state, sizeof(State));
     if (e != hipSuccess) { delete c; return hipfail(e, "hipMalloc(state)"); }
     e = hipMemset(c->d_state, 0, sizeof(State));
@@ -689,8 +694,8 @@ static int estimate_impl(wce_ctx *c, const wce_frames *in, const wce_outputs *ou
         break;
     case wce::SolveStep::RefPilots: rc = wce::launch_mmse_ref_pilots(st, sa, stream); break;
     case wce::SolveStep::RefLsElem: rc = wce::launch_ref_ls_elem(st, sa, la, false, stream); break;
-    case wce::SolveStep::Closed: rc = wce::launch_mmse_rank1(st, sa, false, stream); break;
-    case wce::SolveStep::ClosedNt: rc = wce::launch_mmse_rank1(st, sa, true, stream); break;
+    case wce::SolveStep::Closed: rc = wce::launch_mmse_rank1(st, sa, false, c->cus, stream); break;
+    case wce::SolveStep::ClosedNt: rc = wce::launch_mmse_rank1(st, sa, true, c->cus, stream); break;
     case wce::SolveStep::Factor: rc = wce::launch_mmse_factor(st, sa, r.form, stream); break;
     case wce::SolveStep::Fused: rc = wce::launch_mmse_solve_ls(st, sa, la, r.form, stream); break;
     }
@@ -987,6 +992,12 @@ int wce_event_elapsed_ms(float *ms, void *a, void *b)
 }
 
 }  // extern "C"
+
+extern "C" int wce_debug_rank1_rows_per_sweep(wce_ctx *c)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    return wce::rank1_rows_per_sweep(c->cus);
+}
 
 extern "C" int wce_debug_set_variant(int which, int value)
 {

@@ -217,8 +217,12 @@ int launch_mmse_ref_pilots(const State *st, const SolveArgs &a, void *stream);
 // Dense mmse_solve_kernel<false>
 int launch_mmse_factor(const State *st, const SolveArgs &a, SolveForm form, void *stream);
 // the closed-form bordered rank-1 solve (wce_rank1.hip); nt: nontemporal loads and stores;
-// a.ow2 set: its per-frame-noise build
-int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, void *stream);
+// a.ow2 set: its per-frame-noise build; cus: the device's CU count, read when the context was
+// made (never on this path: plans replay it), which sizes the persistent grid.
+// WCE_VARIANT_R1 = 3..7 pick the launch shape and cache policy here
+int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, int cus, void *stream);
+// units one sweep of its persistent grid covers on a device of `cus` CUs (wce_debug_rank1_rows_per_sweep)
+int rank1_rows_per_sweep(int cus);
 // the same factorisation + LS family + equalization of each frame in one launch (C semantics, one block)
 int launch_mmse_solve_ls(const State *st, const SolveArgs &a, const LsArgs &l, SolveForm form, void *stream);
 // REF pilot form + LS family + equalization, one element per thread; mmse_done: H is already
@@ -292,7 +296,16 @@ constexpr int WCE_VARIANT_R1 = 5;      // PS_MMSE with a rank-1 covariance (TEXT
                                       // 1 = the 53 x 53 factorisation (mmse_solve_fc_kernel, one wave per unit,
                                       // and the fused mmse_solve_ls_kernel), 2 = the closed form with
                                       // nontemporal loads and stores; 0 and 2 bit-identical, 0 and 1 agree to
-                                      // ~1e-11 (each within 1e-10 of the long double answer)
+                                      // ~1e-11 (each within 1e-10 of the long double answer).
+                                      // 3..7 are the closed form to the route planner and are read by
+                                      // launch_mmse_rank1 alone: 3 = one unit per 16-lane row, the grid covers
+                                      // the batch -- what 0 launches too, since the persistent grid measured
+                                      // no faster (DESIGN s6), 4 = the grid capped at 3 workgroups (48 rows
+                                      // per sweep: many ragged trips on a few hundred frames), 5 =
+                                      // nontemporal stores with default loads, 6 = nontemporal loads with
+                                      // default stores (both on the default grid), 7 = the persistent grid:
+                                      // at most 4 workgroups per CU, rows loop with the next unit's loads in
+                                      // flight; all bit-identical to 0
 constexpr int WCE_VARIANT_COUNT = 6;
 int variant_value(int which);
 int set_variant(int which, int value);

@@ -25,8 +25,14 @@
 // instruction moves 256 contiguous bytes of a frame.  The three sums are
 // 16-lane DPP row sums of per-lane partials taken in the order m = 0..3, so a
 // unit's bits depend on its own data only -- not on the batch, its position in
-// it, or its neighbours.  No LDS.  2,544 B of HBM traffic per unit (tx block,
-// rx block, H) against ~400 flop: the kernel is bound by HBM.
+// it, its neighbours, or the launch shape.  No LDS.  2,544 B of HBM traffic per
+// unit (tx block, rx block, H) against ~400 flop: the kernel is bound by memory.
+//
+// By default the grid covers the batch, one unit per row.  A persistent grid (at
+// most R1_WG_PER_CU workgroups per CU, every row looping over units g, g + rows,
+// g + 2 rows, ... with the next unit's tx / rx loads issued before the current
+// unit's sums) is built and tested but measured no faster: WCE_VARIANT_R1 = 7,
+// DESIGN s6.
 #include "wce_internal.h"
 #include "wce_device.h"
 
@@ -45,20 +51,28 @@ __device__ __forceinline__ double2 r1_add(double2 a, double2 b)
     return make_double2(a.x + b.x, a.y + b.y);
 }
 
+// p_k = w_k u_k, the factor of g's terms that the covariance alone decides: |u_k|^2 for
+// w = conj(u).  With a shared u it stays in registers from unit to unit.
+__device__ __forceinline__ double2 rank1_p(double2 u, double2 w, bool cwg)
+{
+#pragma clang fp contract(off)
+    return cwg ? r1_mul(w, u) : make_double2(u.x * u.x + u.y * u.y, 0.0);
+}
+
 // s of one unit.  Lane i of the unit's 16-lane row holds subcarriers i + 16 m
-// in x, r (rx), u, w; entries past subcarrier 52 (and x off State::xmask) are
-// zero.  cwg: w was given (SolveArgs::cw) -- g may be complex; otherwise
-// w = conj(u) and g = a sum |x|^2 |u|^2 is real.  Every lane returns the same bits.
+// in x, r (rx), u, w and p (rank1_p); entries past subcarrier 52 (and x off
+// State::xmask) are zero.  cwg: w was given (SolveArgs::cw) -- g may be complex;
+// otherwise w = conj(u) and g = a sum |x|^2 |u|^2 is real.  Every lane returns the same bits.
 __device__ __forceinline__ double2 rank1_s(const double2 (&x)[4], const double2 (&r)[4], const double2 (&u)[4],
-                                           const double2 (&w)[4], bool cwg, double ac, double bc)
+                                           const double2 (&w)[4], const double2 (&p)[4], bool cwg, double ac,
+                                           double bc)
 {
 #pragma clang fp contract(off)
     double2 g = make_double2(0.0, 0.0), q = g;
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-        const double2 p = cwg ? r1_mul(w[m], u[m]) : make_double2(u[m].x * u[m].x + u[m].y * u[m].y, 0.0);
         const double ax2 = ac * (x[m].x * x[m].x + x[m].y * x[m].y);
-        const double2 gk = make_double2(ax2 * p.x, ax2 * p.y);          // be_k al_k = a |x_k|^2 w_k u_k
+        const double2 gk = make_double2(ax2 * p[m].x, ax2 * p[m].y);    // be_k al_k = a |x_k|^2 w_k u_k
         const double2 qk = r1_mul(r1_mul(w[m], cconj(x[m])), r[m]);     // be_k rx_k
         g = m ? r1_add(g, gk) : gk;
         q = m ? r1_add(q, qk) : qk;
@@ -87,80 +101,207 @@ __device__ __forceinline__ double2 rank1_s(const double2 (&x)[4], const double2 
     return make_double2(t.x + c.x / bc, t.y + c.y / bc);
 }
 
-// One 16-lane row per unit g = frame (or, split, frame * nblk + block): H = u s
-// to row f of a.w, or (split, MATLAB averaging) s_b to a.dots[g] for
-// fc_finish_kernel.  NT: nontemporal tx / rx loads and H stores (A/B).
-// NOISE (wce_estimate_noise): b = a.ow2[f], the frame's own noise variance (TEXTBOOK's b is
-// ow2 itself), one 8-byte load per lane at the row's common address, issued with the other
-// 16.  A frame whose ow2 is not positive and finite gets s = NaN through the same stores
-// (split: a NaN dot, so fc_finish_kernel's mean is NaN): its row is all NaN, and no address
-// depends on the value.  The build without NOISE never reads a.ow2.
-template <bool NT, bool NOISE>
-__global__ __launch_bounds__(256) void mmse_rank1_kernel(const State *__restrict__ st, SolveArgs a)
+// Workgroups resident per CU, and so per CU of the persistent grid: 4 waves per SIMD at up to 128
+// VGPRs, the occupancy every instantiation is held to (DESIGN s6 lists each one's registers).
+constexpr int R1_WG_PER_CU = 4;
+// cache policy of the tx / rx loads and the H stores (A/B, WCE_VARIANT_R1 = 2, 5, 6)
+constexpr int R1_POL_DEFAULT = 0, R1_POL_NT = 1, R1_POL_NT_STORES = 2, R1_POL_NT_LOADS = 3;
+
+// One 16-lane row per unit g = frame (or, SPLIT, frame * nblk + block): H = u s
+// to row f of a.w, or (SPLIT, MATLAB averaging) s_b to a.dots[g] for
+// fc_finish_kernel.  A row takes the units g, g + 16 gridDim.x, ... below `units`.
+// Rows of one wave may make different numbers of trips: the DPP sums stay inside a row.
+// POL: R1_POL_*.  NOISE (wce_estimate_noise): b = a.ow2[f], the frame's own noise
+// variance (TEXTBOOK's b is ow2 itself), one 8-byte load per lane at the row's common
+// address, issued with the unit's other loads.  A frame whose ow2 is not positive and
+// finite gets s = NaN through the same stores (SPLIT: a NaN dot, so fc_finish_kernel's
+// mean is NaN): its row is all NaN, and no address depends on the value.  The build
+// without NOISE never reads a.ow2.
+// SHARED (a.cs == 0, no a.cw): one u for every unit -- u and conj(u) are loaded once per
+// wave, before the loop, and stay in registers (|u|^2 too, except under PF).  Otherwise u
+// (and a given w) are the unit's own and are loaded in its trip.
+// PF (the looping launch shapes, where r1_prefetch allows): the tx / rx loads of the row's
+// next unit are issued before the sums of the current one, under `more` -- no address is
+// formed for a unit past the end, so every address lies in a live unit's block.  Two
+// units' tx / rx and u are 80 of the 128 registers that 4 waves per SIMD leave: the
+// instantiations that hold more (ow2, a unit's own u and w) would spill, and load each
+// unit in its own trip whatever the shape.
+constexpr bool r1_prefetch(bool noise, bool shared) { return shared && !noise; }
+
+template <int POL, bool NOISE, bool SHARED, bool SPLIT, bool PF>
+__global__ __launch_bounds__(256, R1_WG_PER_CU) void mmse_rank1_kernel(const State *__restrict__ st, SolveArgs a)
 {
+    static_assert(!PF || r1_prefetch(NOISE, SHARED), "this instantiation has no registers for a second unit");
+    constexpr bool NTL = POL == R1_POL_NT || POL == R1_POL_NT_LOADS;
+    constexpr bool NTS = POL == R1_POL_NT || POL == R1_POL_NT_STORES;
     const int i = threadIdx.x & 15;
-    const int64_t units = a.split ? a.n * a.nblk : a.n;
-    const int64_t g = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
+    // units < 2^31 (launch_mmse_rank1) and rows <= units + 15: unit and frame indices fit 32 bits
+    const uint32_t units = (uint32_t)(SPLIT ? a.n * a.nblk : a.n);
+    const uint32_t rows = gridDim.x * 16u;
+    uint32_t g = blockIdx.x * 16u + (threadIdx.x >> 4);
     if (g >= units) return;   // whole 16-lane rows: the DPP sums stay inside a live row
-    const int64_t f = a.split ? g / a.nblk : g;
-    const int b = a.split ? (int)(g - f * a.nblk) : 0;
-    const int64_t base = f * a.fs + (int64_t)(a.blk + b) * a.bs;
-    const int64_t cb = f * a.cs;
-    const bool cwg = a.cw != nullptr;
-    const double ac = st->acoef, bc = NOISE ? a.ow2[f] : st->bcoef;
+    const bool cwg = !SHARED && a.cw != nullptr;
+    const double ac = st->acoef;
     const uint64_t xm = st->xmask;
     const double2 zero = make_double2(0.0, 0.0);
-    double2 x[4], r[4], u[4], w[4];
+    // i, hidden from loop-invariant code motion: the per-lane parts of the addresses (a.tx + 16 i, ...) are
+    // three VALU instructions to form again and would otherwise each hold a register pair across the loop
+    auto lane_again = [](int l) __attribute__((always_inline)) {
+        asm volatile("" : "+v"(l));
+        return l;
+    };
+    auto frame_of = [&](uint32_t gu) __attribute__((always_inline)) { return SPLIT ? gu / (uint32_t)a.nblk : gu; };
+    // the tx / rx loads of unit gu and (NOISE) its b, all independent: one memory round trip.  Subcarriers
+    // 48..52 (m = 3) are loaded by lanes 0..4 alone, at the address of the other three plus an immediate,
+    // and are zero in the other lanes
+    auto fetch = [&](uint32_t gu, double2(&xl)[4], double2(&rl)[4], double &bc) __attribute__((always_inline)) {
+        const uint32_t f = frame_of(gu);
+        const int b = SPLIT ? (int)(gu - f * (uint32_t)a.nblk) : 0;
+        const int64_t base = (int64_t)f * a.fs + (int64_t)(a.blk + b) * a.bs + lane_again(i);
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {   // the 16 loads are independent: one memory round trip
-        const int k = i + 16 * m, kc = k < NSC ? k : NSC - 1;
-        const bool live = k < NSC;
-        const double2 xl = NT ? ld2_nt(a.tx, base + kc) : ld2(a.tx, base + kc);
-        const double2 rl = NT ? ld2_nt(a.rx, base + kc) : ld2(a.rx, base + kc);
-        const double2 ul = ld2(a.cu, cb + kc);
-        const double2 wl = cwg ? ld2(a.cw, cb + kc) : cconj(ul);
-        // each array element is written once (a select on an element already stored keeps the array in scratch)
-        x[m] = live && ((xm >> (k & 63)) & 1ull) ? xl : zero;
-        r[m] = live ? rl : zero;
-        u[m] = live ? ul : zero;
-        w[m] = live ? wl : zero;
-    }
-    double2 s = rank1_s(x, r, u, w, cwg, ac, bc);
-    if (NOISE && !(bc > 0.0 && bc < __builtin_inf())) s = make_double2(__builtin_nan(""), __builtin_nan(""));
-    if (a.split) {
-        if (i == 0) st2(a.dots, g, s);
+        for (int m = 0; m < 3; ++m) {
+            xl[m] = NTL ? ld2_nt(a.tx, base + 16 * m) : ld2(a.tx, base + 16 * m);
+            rl[m] = NTL ? ld2_nt(a.rx, base + 16 * m) : ld2(a.rx, base + 16 * m);
+        }
+        xl[3] = zero;
+        rl[3] = zero;
+        if (i < NSC - 48) {
+            xl[3] = NTL ? ld2_nt(a.tx, base + 48) : ld2(a.tx, base + 48);
+            rl[3] = NTL ? ld2_nt(a.rx, base + 48) : ld2(a.rx, base + 48);
+        }
+        if (NOISE) bc = a.ow2[f];
+    };
+    // u, w and p of the unit whose u row starts at cb, loaded like tx / rx: zero past subcarrier 52
+    auto factors = [&](int64_t cb, double2(&u)[4], double2(&w)[4], double2(&p)[4]) __attribute__((always_inline)) {
+        const int64_t ub = cb + i;
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            u[m] = ld2(a.cu, ub + 16 * m);
+            w[m] = cwg ? ld2(a.cw, ub + 16 * m) : cconj(u[m]);
+        }
+        u[3] = zero;
+        w[3] = zero;
+        if (i < NSC - 48) {
+            u[3] = ld2(a.cu, ub + 48);
+            w[3] = cwg ? ld2(a.cw, ub + 48) : cconj(u[3]);
+        }
+#pragma unroll
+        for (int m = 0; m < 4; ++m) p[m] = rank1_p(u[m], w[m], cwg);
+    };
+    double2 u[4], w[4], p[4];
+    if (SHARED) factors(0, u, w, p);
+    // One trip: unit g from (xc, rc, bc) -- loaded here without prefetch -- while unit g + rows loads into
+    // (xn, rn, bn).  False after the row's last unit; otherwise g has moved on.
+    auto trip = [&](double2(&xc)[4], double2(&rc)[4], double &bc, double2(&xn)[4], double2(&rn)[4], double &bn)
+                    __attribute__((always_inline)) {
+        if (!PF) fetch(g, xc, rc, bc);
+        const uint32_t f = frame_of(g);
+        if (!SHARED) factors((int64_t)f * a.cs, u, w, p);
+        const bool more = g + rows < units;
+        if (PF && more) fetch(g + rows, xn, rn, bn);
+        double2 x[4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m)   // subcarriers off State::xmask do not enter X
+            x[m] = (xm >> ((i + 16 * m) & 63)) & 1ull ? xc[m] : zero;
+        // PF: |u|^2 is formed again in every trip, from a u hidden from loop-invariant code motion.  Held
+        // across the trips it is the 8 registers that tip this build into scratch (DESIGN s6); u itself stays
+        double2 pl[4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            double2 um = u[m];
+            if (PF) asm volatile("" : "+v"(um.x), "+v"(um.y));
+            pl[m] = PF ? rank1_p(um, w[m], cwg) : p[m];
+        }
+        double2 s = rank1_s(x, rc, u, w, pl, cwg, ac, bc);
+        if (NOISE && !(bc > 0.0 && bc < __builtin_inf())) s = make_double2(__builtin_nan(""), __builtin_nan(""));
+        if (SPLIT) {
+            if (i == 0) st2(a.dots, g, s);
+        } else {
+            const int64_t hb = (int64_t)f * a.ws + lane_again(i);
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                if (i + 16 * m < NSC) {
+                    const double2 h = r1_mul(u[m], s);
+                    if (NTS) st2_nt(a.w, hb + 16 * m, h);
+                    else st2(a.w, hb + 16 * m, h);
+                }
+            }
+        }
+        g += rows;
+        return more;
+    };
+    double2 xc[4], rc[4], xn[4], rn[4];
+    double bc = st->bcoef, bn = bc;
+    if (!PF) {
+        while (trip(xc, rc, bc, xn, rn, bn)) {}
         return;
     }
+    // The row's first trip stands apart from the loop, so that every later trip starts in one state, whichever
+    // way it was reached: its unit's loads issued a whole trip ago, with only the last trip's stores behind them
+    fetch(g, xc, rc, bc);
+    bool more = trip(xc, rc, bc, xn, rn, bn);
+    while (more) {
+        bc = bn;
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const int k = i + 16 * m;
-        if (k < NSC) {
-            const double2 h = r1_mul(u[m], s);
-            if (NT) st2_nt(a.w, f * a.ws + k, h);
-            else st2(a.w, f * a.ws + k, h);
+        for (int m = 0; m < 4; ++m) {
+            xc[m] = xn[m];
+            rc[m] = rn[m];
         }
+        more = trip(xc, rc, bc, xn, rn, bn);
     }
 }
 
-int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, void *stream)
+int rank1_rows_per_sweep(int cus) { return (cus > 0 ? cus : 256) * R1_WG_PER_CU * 16; }
+
+template <int POL, bool NOISE, bool SHARED>
+static void launch_r1_split(const State *st, const SolveArgs &a, bool pf, dim3 g, hipStream_t s)
+{
+    const dim3 b(256);
+    if constexpr (r1_prefetch(NOISE, SHARED)) {
+        if (pf) {
+            if (a.split) hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, true, true>), g, b, 0, s, st, a);
+            else hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, false, true>), g, b, 0, s, st, a);
+            return;
+        }
+    }
+    if (a.split) hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, true, false>), g, b, 0, s, st, a);
+    else hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, false, false>), g, b, 0, s, st, a);
+}
+template <int POL>
+static void launch_r1_pol(const State *st, const SolveArgs &a, bool pf, dim3 g, hipStream_t s)
+{
+    const bool shared = a.cs == 0 && !a.cw;
+    if (a.ow2) {
+        if (shared) launch_r1_split<POL, true, true>(st, a, pf, g, s);
+        else launch_r1_split<POL, true, false>(st, a, pf, g, s);
+    } else {
+        if (shared) launch_r1_split<POL, false, true>(st, a, pf, g, s);
+        else launch_r1_split<POL, false, false>(st, a, pf, g, s);
+    }
+}
+
+int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, int cus, void *stream)
 {
     if (!a.cu) return WCE_EINVAL;
     if (a.split ? !a.dots : !a.w) return WCE_EINVAL;
     if (a.n <= 0) return WCE_OK;
     if (a.nblk > 1 && !a.split) return WCE_EINVAL;
+    if (a.ow2 && a.cw) return WCE_EINVAL;   // per-frame noise: TEXTBOOK only (check_route_facts), so w = conj(u)
     const int64_t units = a.split ? a.n * a.nblk : a.n;
     if (units > 0x7fffffffll) return WCE_EINVAL;
-    const dim3 g((unsigned)((units + 15) / 16)), b(256);
+    // the launch shape and the A/B cache policies (WCE_VARIANT_R1 = 3..7) are this launcher's alone:
+    // to the route planner they are the closed form
+    const int shape = variant_value(WCE_VARIANT_R1);
+    int64_t wgs = (units + 15) / 16;   // one unit per row: the default, and what a batch below one sweep gets anyway
+    const bool looping = shape == 4 || shape == 7;
+    const int64_t cap = shape == 4 ? 3 : shape == 7 ? rank1_rows_per_sweep(cus) / 16 : wgs;
+    if (wgs > cap) wgs = cap;
+    const dim3 g((unsigned)wgs);
     hipStream_t s = (hipStream_t)stream;
-    if (a.ow2) {   // per-frame noise: TEXTBOOK only (check_route_facts), so w = conj(u)
-        if (a.cw) return WCE_EINVAL;
-        if (nt) hipLaunchKernelGGL((mmse_rank1_kernel<true, true>), g, b, 0, s, st, a);
-        else hipLaunchKernelGGL((mmse_rank1_kernel<false, true>), g, b, 0, s, st, a);
-    } else if (nt) {
-        hipLaunchKernelGGL((mmse_rank1_kernel<true, false>), g, b, 0, s, st, a);
-    } else {
-        hipLaunchKernelGGL((mmse_rank1_kernel<false, false>), g, b, 0, s, st, a);
-    }
+    if (nt) launch_r1_pol<R1_POL_NT>(st, a, looping, g, s);
+    else if (shape == 5) launch_r1_pol<R1_POL_NT_STORES>(st, a, looping, g, s);
+    else if (shape == 6) launch_r1_pol<R1_POL_NT_LOADS>(st, a, looping, g, s);
+    else launch_r1_pol<R1_POL_DEFAULT>(st, a, looping, g, s);
     return hipGetLastError() == hipSuccess ? WCE_OK : WCE_EHIP;
 }
 

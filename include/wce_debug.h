@@ -60,13 +60,27 @@ int wce_debug_set_flat_chunk(long long frames);
  * also asks for LS outputs or equalization runs the LS pass, then this kernel;
  * 1 = the 53 x 53 factorisation, mmse_solve_fc_kernel, one wave per (frame,
  * block), and with LS outputs the fused mmse_solve_ls_kernel; 2 = the closed
- * form with nontemporal loads and stores).
+ * form with nontemporal loads and stores; 3..7 are launch shapes and cache
+ * policies of the closed form, the same route as 0 and read by its launcher
+ * alone: 3 = one unit per 16-lane row, the grid covers the batch, so no row
+ * loops and nothing is prefetched -- the shape 0 launches too; 4 = the grid
+ * capped at 3 workgroups, 48 rows per sweep, so a few hundred frames make
+ * many ragged loop trips; 5 = nontemporal stores with default loads; 6 =
+ * nontemporal loads with default stores; 7 = the persistent grid, at most
+ * wce_debug_rank1_rows_per_sweep rows that loop over the batch with the next
+ * unit's loads in flight -- built, tested and measured no faster than 0).
  * Process-wide; the variants of which 0, 1, 2, 4 give bit-identical results,
  * which 3's kernels sum in different orders and agree to rounding (tests
- * check both); which 5's 0 and 2 are bit-identical, 0 and 1 agree to ~1e-11
+ * check both); which 5's 0 and 2..7 are bit-identical, 0 and 1 agree to ~1e-11
  * (both within 1e-10 of the long double closed form).  (Round 4 retired ls_flat_kernel -- which 1 = 0, 1 -- and the
  * REF frame tiles -- which 0 = 1.) */
 int wce_debug_set_variant(int which, int value);
+/* (frame, block) units one sweep of mmse_rank1_kernel's persistent grid
+ * (which 5 = 7) covers on ctx's device: 16 per workgroup times the workgroups
+ * resident at once (4 per CU, the CU count read when ctx was made).  A larger
+ * batch makes every 16-lane row loop; a smaller one launches one unit per
+ * row.  Negative: an error code. */
+int wce_debug_rank1_rows_per_sweep(struct wce_ctx *ctx);
 /* The kernel families one wce_estimate call launches, in order, as the route
  * planner (csrc/wce_route.h) decides them from these facts: the context's mode,
  * border dot and fusion switches, cm (a constant-modulus operator loaded and

@@ -2,8 +2,9 @@
 buffers in one process: rounds x (variant a, variant b, ...), HIP-event
 timing per launch, outputs compared bit for bit across variants.
 usage: python tools/ab_variant.py {ref,ls,dense,rank1} [--variants 0 1] [--rounds 5] [--reps 20]
-rank1: the TEXTBOOK headline under WCE_VARIANT_R1 (0 closed form, 1 factorisation, 2 closed form, nontemporal);
-0 and 2 are bit-identical, 1 agrees to rounding."""
+rank1: the TEXTBOOK headline under WCE_VARIANT_R1 (0 closed form, 1 factorisation, 2 closed form, nontemporal,
+3 one unit per row like 0, 4 three workgroups, 5 nontemporal stores, 6 nontemporal loads, 7 persistent grid with
+prefetch); 0 and 2..7 are bit-identical, 1 agrees to rounding."""
 import argparse
 import importlib
 import os
