@@ -840,20 +840,35 @@ int wce_synth_frames(wce_ctx *c, wce_complex *tx, wce_complex *rx, wce_complex *
 }
 
 // ---------------------------------------------------------------- front end
-// cfo == null: the plain build (sample_offset is not looked at)
+// the _at calls' window: start[] and capture_len (win); at == false: neither is looked at
+static int check_window(bool at, const int32_t *start, int64_t win, int64_t stride)
+{
+    if (!at) return WCE_OK;
+    if (!start) return fail(WCE_EINVAL, "null start");
+    if (reinterpret_cast<uintptr_t>(start) % 4) return fail(WCE_EINVAL, "start not 4-byte aligned");
+    if (win < 2 * WCE_FFT_SIZE || win >= (int64_t)1 << 31) return fail(WCE_EINVAL, "capture_len outside [128, 2^31)");
+    if (stride < win) return fail(WCE_EINVAL, "capture_stride < capture_len");
+    return WCE_OK;
+}
+
+// cfo == null: the plain build (sample_offset is not looked at).  at: the per-frame-start build, frame f's
+// packet at samples[f*packet_stride + start[f] + 128 + sample_offset] of a window of win samples
 static int front_blocks(wce_ctx *c, const wce_complex *samples, int64_t packet_stride, int64_t n_frames,
                         int32_t n_blocks, const double *cfo, int64_t sample_offset, wce_complex *sym,
-                        int64_t frame_stride, int64_t block_stride, void *stream)
+                        int64_t frame_stride, int64_t block_stride, void *stream, bool at = false,
+                        const int32_t *start = nullptr, int64_t win = 0)
 {
     if (!c) return fail(WCE_EINVAL, "null ctx");
     if (n_frames < 0 || n_blocks < 1) return fail(WCE_EINVAL, "n_frames < 0 or n_blocks < 1");
     if (n_frames == 0) return WCE_OK;
     if (!samples || !sym) return fail(WCE_EINVAL, "null buffer");
-    if (packet_stride < (int64_t)n_blocks * WCE_SAMPLES_PER_BLOCK) return fail(WCE_EINVAL, "packet_stride < 80 n_blocks");
+    if (int rc = check_window(at, start, win, packet_stride)) return rc;
+    if (!at && packet_stride < (int64_t)n_blocks * WCE_SAMPLES_PER_BLOCK)
+        return fail(WCE_EINVAL, "packet_stride < 80 n_blocks");
     if (block_stride < wce::NSC || frame_stride < (int64_t)(n_blocks - 1) * block_stride + wce::NSC)
         return fail(WCE_EINVAL, "output strides too small");
     if (n_frames * n_blocks >= (int64_t)1 << 31) return fail(WCE_EINVAL, "n_frames * n_blocks >= 2^31");
-    if (cfo) {
+    if (cfo || at) {
         if (reinterpret_cast<uintptr_t>(cfo) % 8) return fail(WCE_EINVAL, "cfo not 8-byte aligned");
         if (sample_offset >= (int64_t)1 << 31 || sample_offset <= -((int64_t)1 << 31))
             return fail(WCE_EINVAL, "|sample_offset| >= 2^31");
@@ -865,6 +880,12 @@ static int front_blocks(wce_ctx *c, const wce_complex *samples, int64_t packet_s
     a.n_units = (uint32_t)(n_frames * n_blocks); a.nb = (uint32_t)n_blocks;
     a.cfo = const_cast<double *>(cfo);   // est = 0: read only
     a.n0 = cfo ? sample_offset + a.off : 0;
+    if (at) {   // the packet follows the 128-sample field; the time axis (n0) is the CFO call's
+        a.n0 = sample_offset + a.off;
+        a.off += 2 * WCE_FFT_SIZE + sample_offset;
+        a.start = start; a.win = win;
+        a.span = (int64_t)(n_blocks - 1) * WCE_SAMPLES_PER_BLOCK + WCE_FFT_SIZE;
+    }
     DeviceGuard g(c->device);
     int rc = wce::launch_front(a, false, stream);
     return rc ? fail(rc, "front end launch") : WCE_OK;
@@ -886,15 +907,18 @@ int wce_front_end_blocks_cfo(wce_ctx *c, const wce_complex *samples, int64_t pac
                         block_stride, stream);
 }
 
-// cfo == null: the plain build
+// cfo == null: the plain build.  start != null: the per-frame-start build, lptot the capture windows of
+// lptot_len samples, frame f's field at lptot[f*lptot_stride + start[f] + (0..127)]
 static int front_preamble(wce_ctx *c, const wce_complex *lptot, int64_t lptot_stride, int64_t lptot_len,
                           int64_t n_frames, wce_complex *pre_fft, int64_t pre_stride, double *ow2, double *cfo,
-                          int estimate, void *stream)
+                          int estimate, void *stream, bool at = false, const int32_t *start = nullptr)
 {
     if (!c) return fail(WCE_EINVAL, "null ctx");
     if (n_frames < 0) return fail(WCE_EINVAL, "n_frames < 0");
     if (n_frames == 0) return WCE_OK;
     if (!lptot || !pre_fft) return fail(WCE_EINVAL, "null buffer");
+    if (int rc = check_window(at, start, lptot_len, lptot_stride)) return rc;
+    if (at && estimate && !cfo) return fail(WCE_EINVAL, "estimate without cfo");
     if (lptot_len < 2 * WCE_FFT_SIZE || lptot_stride < lptot_len) return fail(WCE_EINVAL, "lptot_len < 128 or stride < len");
     if (pre_stride < wce::NSC) return fail(WCE_EINVAL, "pre_stride < 53");
     if (n_frames >= (int64_t)1 << 31) return fail(WCE_EINVAL, "n_frames >= 2^31");
@@ -908,6 +932,7 @@ static int front_preamble(wce_ctx *c, const wce_complex *lptot, int64_t lptot_st
     a.cfo = cfo;
     a.n0 = -2 * WCE_FFT_SIZE;   // the long training field ends at n = 0
     a.est = cfo && estimate;
+    if (at) { a.off = 0; a.start = start; a.win = lptot_len; a.span = 2 * WCE_FFT_SIZE; }
     DeviceGuard g(c->device);
     int rc = wce::launch_front(a, true, stream);
     return rc ? fail(rc, "front end launch") : WCE_OK;
@@ -927,6 +952,51 @@ int wce_front_end_preamble_cfo(wce_ctx *c, const wce_complex *lptot, int64_t lpt
     if (!cfo) return fail(WCE_EINVAL, "null cfo");
     return front_preamble(c, lptot, lptot_stride, lptot_len, n_frames, pre_fft, pre_stride, ow2, cfo, estimate,
                           stream);
+}
+
+int wce_front_end_preamble_at(wce_ctx *c, const wce_complex *capture, int64_t capture_stride, int64_t capture_len,
+                              int64_t n_frames, const int32_t *start, wce_complex *pre_fft, int64_t pre_stride,
+                              double *ow2, double *cfo, int estimate, void *stream)
+{
+    return front_preamble(c, capture, capture_stride, capture_len, n_frames, pre_fft, pre_stride, ow2, cfo, estimate,
+                          stream, true, start);
+}
+
+int wce_front_end_blocks_at(wce_ctx *c, const wce_complex *capture, int64_t capture_stride, int64_t capture_len,
+                            int64_t n_frames, int32_t n_blocks, const int32_t *start, const double *cfo,
+                            int64_t sample_offset, wce_complex *sym, int64_t frame_stride, int64_t block_stride,
+                            void *stream)
+{
+    return front_blocks(c, capture, capture_stride, n_frames, n_blocks, cfo, sample_offset, sym, frame_stride,
+                        block_stride, stream, true, start, capture_len);
+}
+
+int wce_front_end_sync(wce_ctx *c, const wce_complex *capture, int64_t capture_stride, int64_t capture_len,
+                       int64_t n_frames, const wce_complex *ltf, double threshold, int32_t backoff, int32_t *start,
+                       double *metric, void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    if (n_frames < 0) return fail(WCE_EINVAL, "n_frames < 0");
+    if (capture_len < 2 * WCE_FFT_SIZE || capture_len >= (int64_t)1 << 31)
+        return fail(WCE_EINVAL, "capture_len outside [128, 2^31)");
+    if (capture_stride < capture_len) return fail(WCE_EINVAL, "capture_stride < capture_len");
+    if (!(threshold >= 0.0 && threshold <= 1.0)) return fail(WCE_EINVAL, "threshold outside [0, 1]");
+    if (backoff < 0 || backoff > 31) return fail(WCE_EINVAL, "backoff outside [0, 31]");
+    if (!start || reinterpret_cast<uintptr_t>(start) % 4) return fail(WCE_EINVAL, "start null or not 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(metric) % 8) return fail(WCE_EINVAL, "metric not 8-byte aligned");
+    if (!ltf || reinterpret_cast<uintptr_t>(ltf) % 16) return fail(WCE_EINVAL, "ltf null or not 16-byte aligned");
+    if (!capture || reinterpret_cast<uintptr_t>(capture) % 16)
+        return fail(WCE_EINVAL, "capture null or not 16-byte aligned");
+    if (n_frames == 0) return WCE_OK;
+    wce::SyncArgs a{};
+    a.capture = reinterpret_cast<const double *>(capture);
+    a.ltf = reinterpret_cast<const double *>(ltf);
+    a.stride = capture_stride; a.len = capture_len; a.n = n_frames;
+    a.threshold = threshold; a.backoff = backoff;
+    a.start = start; a.metric = metric;
+    DeviceGuard g(c->device);
+    int rc = wce::launch_sync(a, c->cus, stream);
+    return rc ? fail(rc, "sync launch") : WCE_OK;
 }
 
 // ---------------------------------------------------------------- runtime helpers

@@ -156,18 +156,27 @@ __device__ __forceinline__ double2 cmul_tw(double2 a, double2 b)
 template <bool PRE>
 __global__ __launch_bounds__(256) void front_kernel(FrontArgs a)
 {
-    constexpr bool CFO = false;
+    constexpr bool CFO = false, AT = false;
 #include "wce_front_body.h"
 }
 // CFO: derotate the samples first (a.cfo, a.n0, a.est).
 template <bool PRE>
 __global__ __launch_bounds__(256) void front_cfo_kernel(FrontArgs a)
 {
-    constexpr bool CFO = true;
+    constexpr bool CFO = true, AT = false;
+#include "wce_front_body.h"
+}
+// AT: the frame's units begin a.start[f] samples into its capture window (a.win, a.span); a frame without
+// a start, or one that would leave its window, reads nothing of it and comes out NaN.  The CFO build's
+// arithmetic with offset 0 where a.cfo is null, so one build serves both.
+template <bool PRE>
+__global__ __launch_bounds__(256) void front_at_kernel(FrontArgs a)
+{
+    constexpr bool CFO = true, AT = true;
 #include "wce_front_body.h"
 }
 
-// a.cfo != null: the CFO builds
+// a.start != null: the per-frame-start builds; else a.cfo != null: the CFO builds
 int launch_front(const FrontArgs &a, bool preamble, void *stream)
 {
     if (a.n_units == 0) return 0;
@@ -175,7 +184,11 @@ int launch_front(const FrontArgs &a, bool preamble, void *stream)
     uint32_t blocks = (a.n_units + units_per_wg - 1) / units_per_wg;
     if (blocks > 256u * 40u) blocks = 256u * 40u;   // grid-stride beyond ~40 workgroups per CU
     const dim3 grid(blocks), blk(256);
-    if (a.cfo && preamble)
+    if (a.start && preamble)
+        hipLaunchKernelGGL(front_at_kernel<true>, grid, blk, 0, (hipStream_t)stream, a);
+    else if (a.start)
+        hipLaunchKernelGGL(front_at_kernel<false>, grid, blk, 0, (hipStream_t)stream, a);
+    else if (a.cfo && preamble)
         hipLaunchKernelGGL(front_cfo_kernel<true>, grid, blk, 0, (hipStream_t)stream, a);
     else if (a.cfo)
         hipLaunchKernelGGL(front_cfo_kernel<false>, grid, blk, 0, (hipStream_t)stream, a);

@@ -1,7 +1,8 @@
-// wce_front_body.h -- the body of front_kernel<PRE> and front_cfo_kernel<PRE>
-// (wce_front.hip), included inside each: `a` is the kernel's FrontArgs, PRE its
-// template parameter, CFO a constexpr bool of the including kernel.  Not a
-// header in its own right.
+// wce_front_body.h -- the body of front_kernel<PRE>, front_cfo_kernel<PRE> and
+// front_at_kernel<PRE> (wce_front.hip), included inside each: `a` is the
+// kernel's FrontArgs, PRE its template parameter, CFO and AT constexpr bools
+// of the including kernel (AT: each frame starts at a.start[f] of its capture
+// window; it implies CFO).  Not a header in its own right.
     __shared__ double2 lds[FE_WAVES][FE_UNITS][64];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int g = lane >> 3, j = lane & 7;
@@ -18,10 +19,19 @@
         const uint32_t u = live ? u0 + g : a.n_units - 1;
         const uint32_t f = u / a.nb, b = u - f * a.nb;
         const double2 *x = src + (int64_t)f * a.ps + a.off + (int64_t)b * 80 + j;
+        bool ok = true;           // AT: the frame has a start and every sample it reads lies in its window
+        if constexpr (AT) {       // one 4-B load per unit; a frame that is not ok reads its window's head
+            const int64_t s = a.start[f], lo = s + a.off;
+            ok = s >= 0 && lo >= 0 && lo + a.span <= a.win;
+            x = src + (int64_t)f * a.ps + (ok ? lo + (int64_t)b * 80 : 0) + j;
+        }
         double2 v[8];
         double s2 = 0.0;
         double e = 0.0;           // CFO: the frame's offset, cycles per sample
-        if constexpr (CFO) {      // one 8-B load at the frame's address, in flight with the samples
+        if constexpr (AT) {       // null cfo: offset 0, the plain call's bits
+            if (a.cfo && !(PRE && a.est)) e = a.cfo[f];
+            if (!ok) e = __builtin_nan("");
+        } else if constexpr (CFO) {   // one 8-B load at the frame's address, in flight with the samples
             if (!(PRE && a.est)) e = a.cfo[f];
         }
         if constexpr (PRE) {      // WiFi_RX.m:24-30: p2 = x[0..64), p1 = x[64..128)
@@ -31,6 +41,7 @@
             if constexpr (CFO) {
                 // z: +0, or NaN when one of the frame's 128 samples is not finite
                 double z = 0.0;
+                if constexpr (AT) z = ok ? 0.0 : __builtin_nan("");
 #pragma unroll
                 for (int n1 = 0; n1 < 8; ++n1)
                     z = fma(p2[n1].x, 0.0, fma(p2[n1].y, 0.0, fma(p1[n1].x, 0.0, fma(p1[n1].y, 0.0, z))));
@@ -49,7 +60,7 @@
                     c = cadd(c, shfl_xor_c(c, 4));   // the same bits on the frame's 8 lanes
                     e = atan2(c.y, c.x) * 0x1.45f306dc9c883p-9;   // 1 / (128 pi)
                     if (live && j == 0) a.cfo[f] = e;
-                } else {
+                } else if (!AT || a.cfo) {   // AT without cfo: samples pass as the plain call passes them
                     z += __shfl_xor(z, 1, 64);
                     z += __shfl_xor(z, 2, 64);
                     z += __shfl_xor(z, 4, 64);

@@ -206,10 +206,29 @@ struct FrontArgs {
     double *cfo;          // [n_frames] cycles per sample; read, or written by the preamble build when est
     int64_t n0;
     int32_t est;          // preamble only: cfo[f] = the two-copy estimate of frame f
+    // per-frame start (null start: the builds above, nothing below is read): src[f*ps ..] is a capture window of
+    // win samples and the frame's units begin start[f] samples into it, unit b at src[f*ps + start[f] + off + 80*b].
+    // The frame reads span samples from start[f] + off; a frame with start[f] < 0, or with one of those samples
+    // outside [0, win), reads the head of its window instead and writes NaN.  These builds take cfo null as offset 0
+    const int32_t *start;
+    int64_t win, span;
+};
+
+// packet detection and symbol timing (wce_sync.hip): frame f's window is capture[f*stride + (0..len-1)]
+struct SyncArgs {
+    const double *capture, *ltf;
+    int64_t stride, len, n;
+    double threshold;
+    int32_t backoff;
+    int32_t *start;
+    double *metric;       // may be null
 };
 
 int launch_ls(const State *st, const LsArgs &a, void *stream);
+// a.start != null: the per-frame-start builds; else a.cfo != null: the CFO builds
 int launch_front(const FrontArgs &a, bool preamble, void *stream);
+// cus: the device's CU count, which caps the grid
+int launch_sync(const SyncArgs &a, int cus, void *stream);
 // PS_MMSE solve launchers: each starts the one kernel family the route (wce_route.h) names.
 // REF pilot form, C semantics (mmse_ref_flat_kernel / mmse_ref_elem_kernel by batch size)
 int launch_mmse_ref_pilots(const State *st, const SolveArgs &a, void *stream);

@@ -132,6 +132,12 @@ ABI = {
                                  c_int64, c_void_p],
     "wce_front_end_preamble_cfo": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p,
                                    c_void_p, c_int, c_void_p],
+    "wce_front_end_sync": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_double, c_int32, c_void_p,
+                           c_void_p, c_void_p],
+    "wce_front_end_preamble_at": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                  c_void_p, c_void_p, c_int, c_void_p],
+    "wce_front_end_blocks_at": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64,
+                                c_void_p, c_int64, c_int64, c_void_p],
     "wce_nonfinite_scan": [c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int64, c_uint32, c_void_p, c_void_p,
                            c_void_p],
     "wce_comm_unique_id": [c_void_p],
@@ -455,11 +461,33 @@ class Context:
                                      pre_stride, first_frame, n_frames, seed, _addr(h_shared), amplitude, ow2,
                                      stream), "wce_synth_frames")
 
+    def front_end_sync(self, capture, n_frames, capture_len, ltf, threshold, backoff=0, start=None, metric=None,
+                       capture_stride=None, stream=None):
+        """wce_front_end_sync: packet detection and symbol timing on raw capture windows (device)
+        [n_frames][capture_stride], against ltf, one clean 64-sample period of the long training symbol
+        (device).  start (device int32 [n_frames]) receives each window's packet start less backoff, or -1
+        below threshold; metric (device float64 [n_frames], optional) the timing metric in [0, 1]."""
+        cs = capture_stride if capture_stride is not None else capture_len
+        _check(_lib.wce_front_end_sync(self.handle, _addr(capture), cs, capture_len, n_frames, _addr(ltf),
+                                       threshold, backoff, _addr(start), _addr(metric), stream),
+               "wce_front_end_sync")
+
     def front_end_blocks(self, samples, n_frames, n_blocks=NBLK, sym=None, packet_stride=None,
-                         frame_stride=NBLK * NSC, block_stride=NSC, stream=None, cfo=None, sample_offset=0):
+                         frame_stride=NBLK * NSC, block_stride=NSC, stream=None, cfo=None, sample_offset=0,
+                         start=None, capture_len=None):
         """Time-domain packets (device) -> 53-bin OFDM symbols (WiFi_blocks_extraction.m).  cfo (a device
         array of n_frames doubles, cycles per sample, e.g. front_end_preamble's): wce_front_end_blocks_cfo,
-        packet sample m derotated as sample m + sample_offset after the end of the long training field."""
+        packet sample m derotated as sample m + sample_offset after the end of the long training field.
+        start (device int32 [n_frames], e.g. front_end_sync's) with capture_len: wce_front_end_blocks_at,
+        samples are capture windows and frame f's packet begins start[f] + 128 + sample_offset into its own."""
+        if start is not None:
+            if capture_len is None:
+                raise ValueError("start needs capture_len")
+            ps = packet_stride if packet_stride is not None else capture_len
+            _check(_lib.wce_front_end_blocks_at(self.handle, _addr(samples), ps, capture_len, n_frames, n_blocks,
+                                                _addr(start), _addr(cfo), sample_offset, _addr(sym), frame_stride,
+                                                block_stride, stream), "wce_front_end_blocks_at")
+            return
         ps = packet_stride if packet_stride is not None else SAMPLES_PER_BLOCK * n_blocks
         if cfo is None:
             _check(_lib.wce_front_end_blocks(self.handle, _addr(samples), ps, n_frames, n_blocks, _addr(sym),
@@ -470,10 +498,20 @@ class Context:
                "wce_front_end_blocks_cfo")
 
     def front_end_preamble(self, lptot, n_frames, lptot_len, pre_fft, ow2=None, lptot_stride=None,
-                           pre_stride=NSC, stream=None, cfo=None, estimate_cfo=True):
+                           pre_stride=NSC, stream=None, cfo=None, estimate_cfo=True, start=None, capture_len=None):
         """Long training fields (device) -> preamble FFT [53] and sigma^2 per frame (WiFi_RX.m:18-30).  cfo (a
         device array of n_frames doubles): wce_front_end_preamble_cfo, which writes each frame's two-copy
-        estimate there (estimate_cfo) or reads it, and derotates the field before anything else."""
+        estimate there (estimate_cfo) or reads it, and derotates the field before anything else.
+        start (device int32 [n_frames], e.g. front_end_sync's): wce_front_end_preamble_at, lptot holds capture
+        windows of capture_len samples (default lptot_len) and frame f's field is the 128 samples at start[f]."""
+        if start is not None:
+            win = capture_len if capture_len is not None else lptot_len
+            ls = lptot_stride if lptot_stride is not None else win
+            _check(_lib.wce_front_end_preamble_at(self.handle, _addr(lptot), ls, win, n_frames, _addr(start),
+                                                  _addr(pre_fft), pre_stride, _addr(ow2), _addr(cfo),
+                                                  1 if (estimate_cfo and cfo is not None) else 0, stream),
+                   "wce_front_end_preamble_at")
+            return
         ls = lptot_stride if lptot_stride is not None else lptot_len
         if cfo is None:
             _check(_lib.wce_front_end_preamble(self.handle, _addr(lptot), ls, lptot_len, n_frames, _addr(pre_fft),
@@ -591,6 +629,44 @@ class Context:
         res["ow2"] = dow2.numpy()
         if cfo:
             res["cfo"] = dcfo.numpy()
+        return res
+
+    def receive_capture_host(self, tx_packets, tx_lptot, rx_capture, threshold, backoff=0, mask=ALL,
+                             semantics=SEM_MATLAB, cfo=False, sample_offset=0):
+        """receive_host with the rx side taken from raw capture windows [B][capture_len], in which each packet
+        (long training field, then sample_offset samples, then the packet) starts at an unknown sample:
+        front_end_sync against tx_lptot[0][-64:] finds each window's start (start - backoff, or -1 where the
+        metric stays below threshold), the front end reads field and packet there, and the estimate follows,
+        all queued on one stream with no host hop.  The dict gains "start" [B] int32 and "metric" [B]; a
+        window without a detected packet, or one the packet does not fit in, gives NaN rows."""
+        pk, lp, cap = _as_c128(tx_packets), _as_c128(tx_lptot), _as_c128(rx_capture)
+        if cap.ndim != 2 or cap.shape[1] < 2 * FFT_SIZE:
+            raise ValueError("rx_capture must be [B][>= 128] complex")
+        B, W = cap.shape
+        if pk.ndim != 2 or pk.shape[0] != B or pk.shape[1] < SAMPLES_PER_BLOCK * NBLK:
+            raise ValueError("tx_packets must be [B][>= 1200] complex")
+        if lp.ndim != 2 or lp.shape[0] != B or lp.shape[1] < 2 * FFT_SIZE:
+            raise ValueError("tx_lptot must be [B][>= 128] complex")
+        dpk, dlp, dcap = DeviceArray.from_numpy(pk), DeviceArray.from_numpy(lp), DeviceArray.from_numpy(cap)
+        dltf = DeviceArray.from_numpy(np.ascontiguousarray(lp[0, -FFT_SIZE:]))
+        dstart, dmetric = DeviceArray((B,), np.int32, zero=True), DeviceArray((B,), np.float64, zero=True)
+        dow2 = DeviceArray((B,), np.float64, zero=True)
+        dcfo = DeviceArray((B,), np.float64, zero=True) if cfo else None
+        sym = [DeviceArray((B, NBLK, NSC), zero=True) for _ in (0, 1)]
+        pre = [DeviceArray((B, NSC), zero=True) for _ in (0, 1)]
+        self.front_end_blocks(dpk, B, NBLK, sym[0], packet_stride=pk.shape[1])
+        self.front_end_preamble(dlp, B, lp.shape[1], pre[0], None)
+        # same (null) stream throughout: each call reads what the one before wrote
+        self.front_end_sync(dcap, B, W, dltf, threshold, backoff, dstart, dmetric)
+        self.front_end_preamble(dcap, B, W, pre[1], dow2, cfo=dcfo, start=dstart)
+        self.front_end_blocks(dcap, B, NBLK, sym[1], cfo=dcfo, sample_offset=sample_offset, start=dstart,
+                              capture_len=W)
+        res = self._estimate_device(sym[0], sym[1], pre[1], B, mask | FRAME_COV, 0, PS_LINEAR, semantics, pre[0],
+                                    False, dow2)
+        res["ow2"] = dow2.numpy()
+        if cfo:
+            res["cfo"] = dcfo.numpy()
+        res["start"], res["metric"] = dstart.numpy(), dmetric.numpy()
         return res
 
 

@@ -342,6 +342,74 @@ int wce_front_end_preamble_cfo(wce_ctx *ctx, const wce_complex *lptot, int64_t l
                                int64_t n_frames, wce_complex *pre_fft, int64_t pre_stride, double *ow2,
                                double *cfo, int estimate, void *stream);
 
+/* ---- packet detection and symbol timing (WiFi_RX.m:7 declares `threshold`,
+ * "Threshold for signal detection"; no reference code uses it) ----
+ * The calls above expect every packet cut out of the sample stream.  These
+ * take raw capture windows instead: frame f's window is
+ *     x[i] = capture[f*capture_stride + i],  i < capture_len,
+ * and the packet starts somewhere inside it.
+ *
+ * wce_front_end_sync finds where.  ltf (device, 64 samples, 16-byte aligned,
+ * shared by all frames) is one clean period of the long training symbol, the
+ * last 64 samples of the transmitted field.  With
+ *     c[d] = sum_{n<64}  x[d+n] conj(ltf[n]),       0 <= d <= capture_len - 64
+ *     E[d] = sum_{n<128} |x[d+n]|^2,  El = sum |ltf[n]|^2
+ *     M[d] = 2 |c[d]| |c[d+64]| / (El E[d]),        0 <= d <= capture_len - 128
+ * (M[d] = 0 where El E[d] == 0; M is in [0, 1] by Cauchy-Schwarz), d* is the
+ * smallest d that attains max M, metric[f] = M[d*] (metric may be NULL), and
+ *     start[f] = d* - backoff   if M[d*] >= threshold and d* - backoff >= 0,
+ *     start[f] = -1             otherwise.
+ * start[f] indexes the first sample of the earlier of the two 64-sample copies
+ * (rx_preamble2 of WiFi_RX.m:26).  The product of the two moduli needs both
+ * copies present at once (half a field scores 0) and ignores the phase turn
+ * between them, but a carrier offset of e cycles per sample costs the metric
+ * sinc^2(64 e): 0.95 at 20 kHz, 0.44 at 77 kHz (10 MHz sampling) -- choose the
+ * threshold with that in mind.  backoff (0..31) moves every FFT window that
+ * many samples into the cyclic prefix, against a strongest path that is not
+ * the first; field and blocks shift alike, so the estimators see one common
+ * phase ramp.  E[d] is summed from non-negative block partials, never as a
+ * running difference: its error is relative to E[d] itself, whatever came
+ * earlier in the window.
+ *
+ * wce_front_end_preamble_at and wce_front_end_blocks_at are the calls above
+ * reading frame f at start[f] (device, n_frames int32): the field is
+ * x[start[f] .. start[f]+128), the earlier copy then the later one; packet
+ * sample m is x[start[f] + 128 + sample_offset + m]; the time axis of the
+ * carrier offset is the same, counted from the end of the field.  cfo == NULL:
+ * no derotation (estimate != 0 then is WCE_EINVAL).  No aligned copy, no extra
+ * pass over the samples: the start is one 4-byte load per unit.
+ *
+ *  - No call reads anything back or waits: sync feeds the _at calls on the
+ *    same stream with no host hop.  The ctx only selects the device.
+ *  - WCE_EINVAL (text in wce_last_error()) before any launch: capture_len <
+ *    128 or >= 2^31; capture_stride < capture_len; threshold not in [0, 1];
+ *    backoff outside [0, 31]; start NULL or not 4-byte aligned; metric not
+ *    8-byte aligned; ltf or capture NULL or not 16-byte aligned; n_frames < 0;
+ *    and, for the _at calls, whatever the calls above reject.
+ *  - sync: a window holding a non-finite sample, or a non-finite ltf, gives
+ *    start[f] = -1 and metric[f] = NaN, for that frame only.
+ *  - _at: a frame with start[f] < 0, or one whose samples would not all lie in
+ *    [0, capture_len), reads nothing outside its window and gets NaN in every
+ *    bin the call writes for it, in its ow2[f] and in its estimated cfo[f]; no
+ *    other frame changes by a bit.  So an undetected packet reaches
+ *    wce_estimate_noise as a NaN row, which wce_nonfinite_scan finds.
+ *  - _at, every other frame: bit-identical to the calls above run on the same
+ *    samples copied into aligned arrays (cfo == NULL: the plain calls on finite
+ *    samples; cfo != NULL: the _cfo calls).
+ *  - A frame's results depend only on its own window and the call's arguments,
+ *    not on its place in the batch or the batch's size; no call reads outside
+ *    [0, capture_len) of any window. */
+int wce_front_end_sync(wce_ctx *ctx, const wce_complex *capture, int64_t capture_stride, int64_t capture_len,
+                       int64_t n_frames, const wce_complex *ltf, double threshold, int32_t backoff,
+                       int32_t *start, double *metric, void *stream);
+int wce_front_end_preamble_at(wce_ctx *ctx, const wce_complex *capture, int64_t capture_stride,
+                              int64_t capture_len, int64_t n_frames, const int32_t *start, wce_complex *pre_fft,
+                              int64_t pre_stride, double *ow2, double *cfo, int estimate, void *stream);
+int wce_front_end_blocks_at(wce_ctx *ctx, const wce_complex *capture, int64_t capture_stride, int64_t capture_len,
+                            int64_t n_frames, int32_t n_blocks, const int32_t *start, const double *cfo,
+                            int64_t sample_offset, wce_complex *sym, int64_t frame_stride, int64_t block_stride,
+                            void *stream);
+
 /* Non-finite guard.  The reference passes NaN/Inf through
  * silently: main.c's PS_MMSE returns NaN x 53 (main.c:148-212), a zero pilot
  * makes PS_* divide by zero (main.c:82-84), and its dimension checks only
