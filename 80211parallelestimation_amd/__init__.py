@@ -9,6 +9,7 @@ from .wce import (  # noqa: F401
     PS_MMSE, PS_SINC, SEM_C, SEM_MATLAB, Context, DeviceArray, PinnedArray, Event, Frames, Outputs, Stream, WceError, device_count, load,
     state_blob, state_mode, cov_factor, debug_route, synchronize, ldc_to_complex, complex_to_ldc, WiFi_channel_estimation_LT_LS, WiFi_channel_estimation_PS_Cubic,
     WiFi_channel_estimation_PS_Linear, WiFi_channel_estimation_PS_MMSE, WiFi_channel_estimation_PS_Sinc,
+    DEMOD_REF_TX, DEMOD_TRACK, MOD_BPSK, MOD_QAM16, MOD_QAM64, MOD_QPSK, Demod, DemodOut,
 )
 
 __version__ = "0.1.0"

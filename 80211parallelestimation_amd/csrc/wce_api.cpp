@@ -999,6 +999,65 @@ int wce_front_end_sync(wce_ctx *c, const wce_complex *capture, int64_t capture_s
     return rc ? fail(rc, "sync launch") : WCE_OK;
 }
 
+// ---------------------------------------------------------------- demodulation
+int wce_demodulate(wce_ctx *c, const wce_frames *in, const wce_demod *p, const wce_demod_out *out, void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    if (!in || !p || !out) return fail(WCE_EINVAL, "wce_demodulate: null frames, parameters or outputs");
+    if (!in->tx || !in->rx) return fail(WCE_EINVAL, "wce_demodulate: tx/rx required");
+    if (!p->h) return fail(WCE_EINVAL, "wce_demodulate: h required");
+    if (!out->eq && !out->sym && !out->theta && !out->evm && !out->nerr)
+        return fail(WCE_EINVAL, "wce_demodulate: no output requested");
+    if (p->h_stride < wce::NSC) return fail(WCE_EINVAL, "wce_demodulate: h_stride < 53");
+    double K;
+    switch (p->modulation) {   // the doubles nearest to 1 / sqrt(1, 2, 10, 42)
+    case WCE_MOD_BPSK: K = 1.0; break;
+    case WCE_MOD_QPSK: K = 0.70710678118654752440; break;
+    case WCE_MOD_QAM16: K = 0.31622776601683793320; break;
+    case WCE_MOD_QAM64: K = 0.15430334996209191026; break;
+    default: return fail(WCE_EINVAL, "wce_demodulate: unknown modulation");
+    }
+    if (p->flags & ~(WCE_DEMOD_TRACK | WCE_DEMOD_REF_TX)) return fail(WCE_EINVAL, "wce_demodulate: unknown flag bits");
+    if (!(p->scale > 0.0) || p->scale * 0.0 != 0.0) return fail(WCE_EINVAL, "wce_demodulate: scale not positive and finite");
+    // the frames: the fields the call reads (block, semantics and the preambles are ignored)
+    wce_frames fr = *in;
+    fr.rx_pre = fr.tx_pre = nullptr;
+    fr.block = 0;
+    fr.semantics = WCE_SEM_C;
+    int rc = check_frames(&fr, true);
+    if (rc) return rc;
+    const int64_t n = in->n_frames;
+    const int64_t span = (wce::NBLK - 1);
+    if (out->eq && (out->eq_block_stride < wce::NSC ||
+                    (n > 1 && out->eq_frame_stride < span * out->eq_block_stride + wce::NSC)))
+        return fail(WCE_EINVAL, "wce_demodulate: eq strides too small");
+    if (out->sym && (out->sym_block_stride < wce::NSC ||
+                     (n > 1 && out->sym_frame_stride < span * out->sym_block_stride + wce::NSC)))
+        return fail(WCE_EINVAL, "wce_demodulate: sym strides too small");
+    if (reinterpret_cast<uintptr_t>(out->theta) % 8 || reinterpret_cast<uintptr_t>(out->evm) % 8)
+        return fail(WCE_EINVAL, "wce_demodulate: theta or evm not 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out->nerr) % 4) return fail(WCE_EINVAL, "wce_demodulate: nerr not 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(p->h) % 16 || reinterpret_cast<uintptr_t>(p->h_lt) % 16 ||
+        reinterpret_cast<uintptr_t>(out->eq) % 16)
+        return fail(WCE_EINVAL, "wce_demodulate: h, h_lt or eq not 16-byte aligned");
+    if (n == 0) return WCE_OK;
+    wce::DemodArgs a{};
+    a.tx = reinterpret_cast<const double *>(in->tx);
+    a.rx = reinterpret_cast<const double *>(in->rx);
+    a.h = reinterpret_cast<const double *>(p->h);
+    a.hlt = reinterpret_cast<const double *>(p->h_lt);
+    a.fs = in->frame_stride; a.bs = in->block_stride; a.hs = p->h_stride; a.n = n;
+    a.mod = p->modulation; a.flags = p->flags;
+    a.scale = p->scale; a.d = p->scale * K;
+    a.eq = reinterpret_cast<double *>(out->eq);
+    a.sym = out->sym; a.theta = out->theta; a.evm = out->evm; a.nerr = out->nerr;
+    a.eqfs = out->eq_frame_stride; a.eqbs = out->eq_block_stride;
+    a.symfs = out->sym_frame_stride; a.symbs = out->sym_block_stride;
+    DeviceGuard g(c->device);
+    rc = wce::launch_demod(a, stream);
+    return rc ? fail(rc, "demod launch") : WCE_OK;
+}
+
 // ---------------------------------------------------------------- runtime helpers
 int wce_device_count(int *count)
 {

@@ -224,7 +224,22 @@ struct SyncArgs {
     double *metric;       // may be null
 };
 
+// demodulation (wce_demod.hip): frames as LsArgs; h / hlt rows of stride hs (hlt null: no blend)
+struct DemodArgs {
+    const double *tx, *rx, *h, *hlt;
+    int64_t fs, bs, hs, n;
+    int32_t mod;          // WCE_MOD_*: bits per data symbol
+    uint32_t flags;       // WCE_DEMOD_*
+    double scale, d;      // pilot and data level half-spacing: scale, scale K
+    double *eq;           // each output may be null
+    uint8_t *sym;
+    double *theta, *evm;
+    uint32_t *nerr;
+    int64_t eqfs, eqbs, symfs, symbs;
+};
+
 int launch_ls(const State *st, const LsArgs &a, void *stream);
+int launch_demod(const DemodArgs &a, void *stream);
 // a.start != null: the per-frame-start builds; else a.cfo != null: the CFO builds
 int launch_front(const FrontArgs &a, bool preamble, void *stream);
 // cus: the device's CU count, which caps the grid

@@ -42,6 +42,9 @@ FFT_SIZE = 64            # front end: 64-point DFT per OFDM block (WiFi_RX.m:10)
 SAMPLES_PER_BLOCK = 80   # 64 + 16-sample cyclic prefix (WiFi_RX.m:12)
 SEM_C = 0          # main.c semantics
 SEM_MATLAB = 1     # WiFi_channel_estimation_*.m semantics
+MOD_BPSK, MOD_QPSK, MOD_QAM16, MOD_QAM64 = 1, 2, 4, 6   # wce_demod.modulation: bits per data symbol
+DEMOD_TRACK = 1 << 0     # remove each block's common pilot phase
+DEMOD_REF_TX = 1 << 1    # EVM against tx instead of the decided point
 
 STATUS = {0: "ok", -1: "invalid argument", -2: "HIP error", -3: "out of memory",
           -4: "context state not ready", -5: "no gfx950 device"}
@@ -80,6 +83,19 @@ class Outputs(ctypes.Structure):
                 ("ps_mmse", c_void_p), ("eq", c_void_p), ("out_stride", c_int64),
                 ("eq_frame_stride", c_int64), ("eq_block_stride", c_int64), ("eq_source", c_uint32),
                 ("flags", c_uint32)]
+
+
+class Demod(ctypes.Structure):
+    """struct wce_demod (include/wce.h)."""
+    _fields_ = [("h", c_void_p), ("h_lt", c_void_p), ("h_stride", c_int64), ("modulation", c_int32),
+                ("flags", c_uint32), ("scale", c_double)]
+
+
+class DemodOut(ctypes.Structure):
+    """struct wce_demod_out (include/wce.h)."""
+    _fields_ = [("eq", c_void_p), ("sym", c_void_p), ("theta", c_void_p), ("evm", c_void_p), ("nerr", c_void_p),
+                ("eq_frame_stride", c_int64), ("eq_block_stride", c_int64), ("sym_frame_stride", c_int64),
+                ("sym_block_stride", c_int64)]
 
 
 _lib = None
@@ -138,6 +154,7 @@ ABI = {
                                   c_void_p, c_void_p, c_int, c_void_p],
     "wce_front_end_blocks_at": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64,
                                 c_void_p, c_int64, c_int64, c_void_p],
+    "wce_demodulate": [c_void_p, POINTER(Frames), POINTER(Demod), POINTER(DemodOut), c_void_p],
     "wce_nonfinite_scan": [c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int64, c_uint32, c_void_p, c_void_p,
                            c_void_p],
     "wce_comm_unique_id": [c_void_p],
@@ -449,6 +466,44 @@ class Context:
         _check(_lib.wce_estimate_noise(self.handle, byref(frames), byref(outputs), mask, _addr(ow2), stream),
                "wce_estimate_noise")
 
+    def demodulate(self, frames: Frames, h, h_lt=None, h_stride=NSC, modulation=MOD_BPSK, scale=8.8753, track=True,
+                   ref_tx=True, eq=None, sym=None, theta=None, evm=None, nerr=None, stream=None,
+                   eq_frame_stride=None, eq_block_stride=NSC, sym_frame_stride=None, sym_block_stride=NSC):
+        """wce_demodulate on device arrays: equalize `frames` with the estimate h [n][h_stride] (blended with
+        h_lt over the blocks, if given), remove each block's common pilot phase (track), slice to `modulation`
+        and score.  Outputs, each optional: eq complex [n][15][53], sym uint8 [n][15][53] (Gray labels, 0xFF
+        where the symbol is not finite), theta float64 [n][15], evm float64 [n] (against tx with ref_tx, else
+        against the decided points), nerr uint32 [n].  Frame strides default to 15 block strides."""
+        p = Demod(_addr(h), _addr(h_lt), h_stride, modulation,
+                  (DEMOD_TRACK if track else 0) | (DEMOD_REF_TX if ref_tx else 0), scale)
+        o = DemodOut(_addr(eq), _addr(sym), _addr(theta), _addr(evm), _addr(nerr),
+                     eq_frame_stride if eq_frame_stride is not None else NBLK * eq_block_stride, eq_block_stride,
+                     sym_frame_stride if sym_frame_stride is not None else NBLK * sym_block_stride, sym_block_stride)
+        _check(_lib.wce_demodulate(self.handle, byref(frames), byref(p), byref(o), stream), "wce_demodulate")
+
+    def _demod_device(self, fr, B, dh, dhlt, modulation, scale, track, ref_tx):
+        """queue demodulate with every output; -> name -> DeviceArray (read them after a synchronize)"""
+        d = {"eq": DeviceArray((B, NBLK, NSC), zero=True), "sym": DeviceArray((B, NBLK, NSC), np.uint8, zero=True),
+             "theta": DeviceArray((B, NBLK), np.float64, zero=True), "evm": DeviceArray((B,), np.float64, zero=True),
+             "nerr": DeviceArray((B,), np.uint32, zero=True)}
+        self.demodulate(fr, dh, dhlt, NSC, modulation, scale, track, ref_tx, **d)
+        return d
+
+    def demodulate_host(self, tx, rx, h, h_lt=None, modulation=MOD_BPSK, scale=8.8753, track=True, ref_tx=True):
+        """Convenience: host frames [B][15][53] and estimates h (and h_lt) [B][53] -> dict of host arrays
+        eq, sym, theta, evm, nerr."""
+        tx, rx, h = _as_c128(tx), _as_c128(rx), _as_c128(h)
+        B = tx.shape[0]
+        if tx.shape != (B, NBLK, NSC) or rx.shape != tx.shape:
+            raise ValueError("tx/rx must be [B][15][53] complex")
+        if h.shape != (B, NSC) or (h_lt is not None and np.shape(h_lt) != (B, NSC)):
+            raise ValueError("h / h_lt must be [B][53] complex")
+        dtx, drx, dh = DeviceArray.from_numpy(tx), DeviceArray.from_numpy(rx), DeviceArray.from_numpy(h)
+        dhlt = DeviceArray.from_numpy(_as_c128(h_lt)) if h_lt is not None else None
+        d = self._demod_device(self.frames(dtx, drx, B), B, dh, dhlt, modulation, scale, track, ref_tx)
+        synchronize()
+        return {n: a.numpy() for n, a in d.items()}
+
     def mmse_solve(self, frames: Frames, W, w_stride=NSC, stream=None):
         _check(_lib.wce_mmse_solve(self.handle, byref(frames), _addr(W), w_stride, stream), "wce_mmse_solve")
 
@@ -568,9 +623,10 @@ class Context:
         dtp = DeviceArray.from_numpy(_as_c128(tx_pre)) if tx_pre is not None else None
         return self._estimate_device(dtx, drx, dpre, B, mask, block, eq_source, semantics, dtp, ls_f32, dow2)
 
-    def _estimate_device(self, dtx, drx, dpre, B, mask, block, eq_source, semantics, dtp, ls_f32, dow2):
+    def _estimate_device(self, dtx, drx, dpre, B, mask, block, eq_source, semantics, dtp, ls_f32, dow2, demod=None):
         """estimate_host's device half: dense [B][15][53] frames (and rx_pre [B][53], tx_pre [53], ow2 [B] or
-        None) on the device -> dict of host outputs"""
+        None) on the device -> dict of host outputs.  demod: (source bit, modulation, scale, track) queues
+        demodulate behind the estimate with h = that estimator's output and h_lt = lt_ls; the dict gains "demod"."""
         names = [("lt_ls", LT_LS), ("ps_linear", PS_LINEAR), ("ps_cubic", PS_CUBIC), ("ps_sinc", PS_SINC),
                  ("ps_mmse", PS_MMSE)]
         lsdt = np.complex64 if ls_f32 else np.complex128
@@ -582,14 +638,31 @@ class Context:
                     OUT_LS_F32 if ls_f32 else 0)
         fr = self.frames(dtx, drx, B, rx_pre=dpre, block=block, semantics=semantics, tx_pre=dtp)
         self.estimate(fr, o, mask, ow2=dow2)
+        dem = None
+        if demod is not None:   # same (null) stream: it reads the estimate's outputs in order, no host hop
+            src = {bit: n for n, bit in names}[demod[0]]
+            dem = self._demod_device(fr, B, outs[src], outs["lt_ls"], demod[1], demod[2], demod[3], True)
         synchronize()
         res = {n: outs[n].numpy() for n in outs}
         if deq is not None:
             res["eq"] = deq.numpy()
+        if dem is not None:
+            res["demod"] = {n: a.numpy() for n, a in dem.items()}
         return res
 
+    @staticmethod
+    def _demod_request(demod_source, mask, modulation, scale, track):
+        """receive_host's demod_source: None, or one estimator bit that `mask` holds beside LT_LS"""
+        if demod_source is None:
+            return None
+        if demod_source not in (LT_LS, PS_LINEAR, PS_CUBIC, PS_SINC, PS_MMSE):
+            raise ValueError("demod_source must be one estimator bit")
+        if not (mask & demod_source) or not (mask & LT_LS):
+            raise ValueError("demod_source and LT_LS must be in mask")
+        return (demod_source, modulation, scale, track)
+
     def receive_host(self, tx_packets, tx_lptot, rx_packets, rx_lptot, mask=ALL, semantics=SEM_MATLAB, cfo=False,
-                     sample_offset=0):
+                     sample_offset=0, demod_source=None, modulation=MOD_BPSK, scale=8.8753, track=True):
         """WiFi_RX.m:17-60 for a batch, on the device with no host hop in between: host time-domain packets
         [B][>= 1200] and long training fields [B][L] of both sides -> the front end (symbols, preamble FFTs and
         each packet's sigma^2) -> estimate with each frame's own rx preamble (WCE_MMSE_FRAME_COV) and own
@@ -599,7 +672,12 @@ class Context:
         cfo: each received packet's carrier frequency offset is estimated from its long training field and
         removed from the field and the packet (which starts sample_offset samples after the field) before
         anything else, on the same stream; the dict gains "cfo" [B], cycles per sample.  The tx side is the
-        clean reference and is never derotated."""
+        clean reference and is never derotated.
+        demod_source: an estimator bit of `mask` (PS_MMSE included; LT_LS must be in mask too): the frames are
+        demodulated with h = that estimator's output and h_lt = the frame's lt_ls (demodulate: `modulation`,
+        `scale`, `track`, EVM against tx), queued behind the estimate; the dict gains "demod", the dict of
+        demodulate_host.  None: no demodulation."""
+        dem = self._demod_request(demod_source, mask, modulation, scale, track)
         pk = [_as_c128(tx_packets), _as_c128(rx_packets)]
         lp = [_as_c128(tx_lptot), _as_c128(rx_lptot)]
         B = pk[1].shape[0]
@@ -625,20 +703,24 @@ class Context:
             pre.append(dpre)
         # same (null) stream throughout: the estimate reads the front end's outputs in order
         res = self._estimate_device(sym[0], sym[1], pre[1], B, mask | FRAME_COV, 0, PS_LINEAR, semantics, pre[0],
-                                    False, dow2)
+                                    False, dow2, dem)
         res["ow2"] = dow2.numpy()
         if cfo:
             res["cfo"] = dcfo.numpy()
         return res
 
     def receive_capture_host(self, tx_packets, tx_lptot, rx_capture, threshold, backoff=0, mask=ALL,
-                             semantics=SEM_MATLAB, cfo=False, sample_offset=0):
+                             semantics=SEM_MATLAB, cfo=False, sample_offset=0, demod_source=None,
+                             modulation=MOD_BPSK, scale=8.8753, track=True):
         """receive_host with the rx side taken from raw capture windows [B][capture_len], in which each packet
         (long training field, then sample_offset samples, then the packet) starts at an unknown sample:
         front_end_sync against tx_lptot[0][-64:] finds each window's start (start - backoff, or -1 where the
         metric stays below threshold), the front end reads field and packet there, and the estimate follows,
         all queued on one stream with no host hop.  The dict gains "start" [B] int32 and "metric" [B]; a
-        window without a detected packet, or one the packet does not fit in, gives NaN rows."""
+        window without a detected packet, or one the packet does not fit in, gives NaN rows.
+        demod_source, modulation, scale, track: as receive_host; such a window's "demod" has NaN evm and
+        0xFF symbols."""
+        dem = self._demod_request(demod_source, mask, modulation, scale, track)
         pk, lp, cap = _as_c128(tx_packets), _as_c128(tx_lptot), _as_c128(rx_capture)
         if cap.ndim != 2 or cap.shape[1] < 2 * FFT_SIZE:
             raise ValueError("rx_capture must be [B][>= 128] complex")
@@ -662,7 +744,7 @@ class Context:
         self.front_end_blocks(dcap, B, NBLK, sym[1], cfo=dcfo, sample_offset=sample_offset, start=dstart,
                               capture_len=W)
         res = self._estimate_device(sym[0], sym[1], pre[1], B, mask | FRAME_COV, 0, PS_LINEAR, semantics, pre[0],
-                                    False, dow2)
+                                    False, dow2, dem)
         res["ow2"] = dow2.numpy()
         if cfo:
             res["cfo"] = dcfo.numpy()

@@ -410,6 +410,77 @@ int wce_front_end_blocks_at(wce_ctx *ctx, const wce_complex *capture, int64_t ca
                             int64_t sample_offset, wce_complex *sym, int64_t frame_stride, int64_t block_stride,
                             void *stream);
 
+/* ---- demodulation: pilot phase tracking, slicer, EVM (the reference's README
+ * applies the estimate "before the symbols are decoded"; WiFi_Equalization.m
+ * stops at the equalized symbols) ----
+ * wce_demodulate equalizes frame f with any channel estimate the caller holds,
+ * h[f*h_stride + k] (a wce_outputs array, PS_MMSE included), removes each
+ * block's common phase, decides every symbol and scores the frame.  It reads
+ * in->tx, in->rx, the strides and n_frames; rx_pre, tx_pre, block and
+ * semantics are ignored.  The ctx only selects the device.
+ *
+ * Frame f, block b = 0..14, subcarrier k != 26 (k = 26 is DC: eq = 0, sym = 0);
+ * pilots P = {5, 19, 33, 47}:
+ *   blend     h_lt == NULL: Hu_b = h.  Else Hu_b = ((15-(b+1))/15) h_lt + ((b+1)/15) h
+ *             (WiFi_Equalization.m:4-5), in WCE_EQUALIZE's operation order.
+ *   tracking  (WCE_DEMOD_TRACK) z_b = sum_{p in P, ascending} rx_b[p] conj(Hu_b[p] tx_b[p]),
+ *             theta_b = atan2(Im z_b, Re z_b) in (-pi, pi], rotor r_b = conj(z_b) / |z_b|;
+ *             z_b = 0: r_b = 1, theta_b = 0.  Without the flag r_b = 1, theta_b = 0.
+ *             This is the maximum-likelihood common phase: each pilot weighs |H|^2 |x|^2.
+ *   equalize  e_b[k] = (rx_b[k] / Hu_b[k]) r_b; where r_b = 1 the product is skipped, so
+ *             with h_lt = the frame's lt_ls and h = a PS estimate an untracked eq is
+ *             WCE_EQUALIZE's, bit for bit.
+ *   slice     d = scale K, K the double nearest to 1, 1/sqrt 2, 1/sqrt 10, 1/sqrt 42 for
+ *             BPSK, QPSK, 16-QAM, 64-QAM.  An axis of M levels (2, 2, 4, 8): level
+ *             i = clamp(floor(v / (2d) + M/2), 0, M-1), decided coordinate (2i - (M-1)) d;
+ *             v / (2d) is taken as v times the double 1 / (2d), so a coordinate within
+ *             an ulp of a boundary may fall either way.  Gray label g(i) = i ^ (i >> 1)
+ *             (802.11's 16- and 64-QAM tables, b0 first); sym = g(i_I) << (bits/2) | g(i_Q).
+ *             BPSK slices the real axis only (sym = i_I, decided point on the real axis);
+ *             pilots are sliced as BPSK with d = scale whatever `modulation` is.
+ *   score     over the 48 x 15 data symbols: evm[f] = sqrt(sum |e - ref|^2 / sum |ref|^2),
+ *             ref = the tx symbol (WCE_DEMOD_REF_TX) or the decided point; nerr[f] = the
+ *             number of data symbols whose sym differs from the sym of the tx symbol put
+ *             through the same slicer.
+ *
+ *  - A symbol whose e is not finite gets sym = 0xFF and counts in nerr; a frame with
+ *    such a data symbol gets evm = NaN.  No other frame changes by a bit.
+ *  - A frame's bits depend only on its own data and the call's arguments, not on
+ *    its place in the batch or the batch's size.
+ *  - Asynchronous on `stream`; nothing is read back, so it follows wce_estimate on
+ *    the same stream with no host hop.  Absent outputs cost no stores.
+ *  - WCE_EINVAL (text in wce_last_error()) before any launch: a NULL in, p, out,
+ *    p->h, in->tx or in->rx; every output NULL; h_stride < 53; an unknown
+ *    modulation or flag bit; scale not positive and finite; eq or sym strides
+ *    too small (block stride < 53, or, with more than one frame, frame stride <
+ *    14 block strides + 53); theta or evm not 8-byte aligned; nerr not 4-byte
+ *    aligned; h, h_lt or eq not 16-byte aligned; n_frames < 0 or > 2^31 - 1; the
+ *    frames' block_stride < 53 or, with more than one frame, frame_stride < 14
+ *    block strides + 53.  n_frames == 0 is WCE_OK. */
+enum { WCE_MOD_BPSK = 1, WCE_MOD_QPSK = 2, WCE_MOD_QAM16 = 4, WCE_MOD_QAM64 = 6 };  /* bits per symbol */
+#define WCE_DEMOD_TRACK  (1u << 0)   /* remove each block's common pilot phase */
+#define WCE_DEMOD_REF_TX (1u << 1)   /* EVM against in->tx instead of the decided point */
+
+typedef struct {
+    const wce_complex *h;     /* device; h[f*h_stride + k]: any complex-double estimate, e.g. a wce_outputs array */
+    const wce_complex *h_lt;  /* device, same stride; NULL = no blend */
+    int64_t h_stride;         /* >= 53 */
+    int32_t modulation;       /* WCE_MOD_*, of the 48 data subcarriers (pilots are BPSK) */
+    uint32_t flags;           /* WCE_DEMOD_* */
+    double scale;             /* amplitude of a unit-energy constellation point in eq units (inputs.h: 8.8753) */
+} wce_demod;
+
+typedef struct {              /* every pointer device, each may be NULL = not wanted */
+    wce_complex *eq;          /* eq[f*eq_frame_stride + b*eq_block_stride + k] */
+    uint8_t *sym;             /* sym[f*sym_frame_stride + b*sym_block_stride + k] */
+    double *theta;            /* theta[f*15 + b], radians, (-pi, pi] */
+    double *evm;              /* evm[f] */
+    uint32_t *nerr;           /* nerr[f] */
+    int64_t eq_frame_stride, eq_block_stride, sym_frame_stride, sym_block_stride;
+} wce_demod_out;
+
+int wce_demodulate(wce_ctx *ctx, const wce_frames *in, const wce_demod *p, const wce_demod_out *out, void *stream);
+
 /* Non-finite guard.  The reference passes NaN/Inf through
  * silently: main.c's PS_MMSE returns NaN x 53 (main.c:148-212), a zero pilot
  * makes PS_* divide by zero (main.c:82-84), and its dimension checks only
