@@ -20,7 +20,9 @@
 // that arithmetic is pinned by the CPU model alone (tests/test_rank1_model.py
 // against the mpmath fixture tests/golden/rank1_cw_mp.npz).
 //
-// 16 lanes per (frame, block) unit, 16 units per 256-thread workgroup.  Lane i
+// 16 lanes per (frame, block) unit, 16 units per 256-thread workgroup (8 or 4 in the
+// 128- and 64-thread launch shapes: no LDS and no barrier, so the size only decides how
+// many waves must retire before a workgroup slot is refilled).  Lane i
 // owns subcarriers i, i + 16, i + 32, i + 48 (< 53): every load and store
 // instruction moves 256 contiguous bytes of a frame.  The three sums are
 // 16-lane DPP row sums of per-lane partials taken in the order m = 0..3, so a
@@ -33,6 +35,10 @@
 // g + 2 rows, ... with the next unit's tx / rx loads issued before the current
 // unit's sums) is built and tested but measured no faster: WCE_VARIANT_R1 = 7,
 // DESIGN s6.
+//
+// A wave's prologue is one scalar round trip (the kernel arguments, a.n among them),
+// the bounds test, and then every vector load of its first unit: tx / rx first, the
+// shared u behind them, one wait chain in front of the arithmetic.
 #include "wce_internal.h"
 #include "wce_device.h"
 
@@ -106,10 +112,13 @@ __device__ __forceinline__ double2 rank1_s(const double2 (&x)[4], const double2 
 constexpr int R1_WG_PER_CU = 4;
 // cache policy of the tx / rx loads and the H stores (A/B, WCE_VARIANT_R1 = 2, 5, 6)
 constexpr int R1_POL_DEFAULT = 0, R1_POL_NT = 1, R1_POL_NT_STORES = 2, R1_POL_NT_LOADS = 3;
+// the default cache policy behind the previous prologue (A/B, WCE_VARIANT_R1 = 10): u and the State scalars
+// are loaded and waited for before the first tx / rx load is issued
+constexpr int R1_POL_U_FIRST = 4;
 
 // One 16-lane row per unit g = frame (or, SPLIT, frame * nblk + block): H = u s
 // to row f of a.w, or (SPLIT, MATLAB averaging) s_b to a.dots[g] for
-// fc_finish_kernel.  A row takes the units g, g + 16 gridDim.x, ... below `units`.
+// fc_finish_kernel.  A row takes the units g, g + rows, ... below `units`, rows = gridDim.x blockDim.x / 16.
 // Rows of one wave may make different numbers of trips: the DPP sums stay inside a row.
 // POL: R1_POL_*.  NOISE (wce_estimate_noise): b = a.ow2[f], the frame's own noise
 // variance (TEXTBOOK's b is ow2 itself), one 8-byte load per lane at the row's common
@@ -134,15 +143,36 @@ __global__ __launch_bounds__(256, R1_WG_PER_CU) void mmse_rank1_kernel(const Sta
     static_assert(!PF || r1_prefetch(NOISE, SHARED), "this instantiation has no registers for a second unit");
     constexpr bool NTL = POL == R1_POL_NT || POL == R1_POL_NT_LOADS;
     constexpr bool NTS = POL == R1_POL_NT || POL == R1_POL_NT_STORES;
+    constexpr bool LF = POL != R1_POL_U_FIRST;   // loads first
     const int i = threadIdx.x & 15;
+    const uint32_t rpw = blockDim.x >> 4;   // rows per workgroup: 16, 8 or 4
+    int64_t n = a.n;
+    if (LF) {
+        // The launch shape and every argument an address needs are inputs of an empty asm that hands n on
+        // to the bounds test, so they are in SGPRs ahead of the branch: one batch of scalar loads, where
+        // the compiler would fetch a.n alone, wait, branch, and only then start on the rest.  Not volatile
+        // and inputs only: the pointers keep their address spaces, and the loads through st stay scalar
+        auto held = [](int64_t &c, auto v) __attribute__((always_inline)) { asm("" : "+s"(c) : "s"(v)); };
+        held(n, st), held(n, a.tx), held(n, a.rx), held(n, a.fs), held(n, a.bs), held(n, a.blk), held(n, a.cu);
+        held(n, rpw), held(n, gridDim.x);
+        if (SPLIT) held(n, a.nblk), held(n, a.dots);
+        else held(n, a.w), held(n, a.ws);
+        if (NOISE) held(n, a.ow2);
+        if (!SHARED) held(n, a.cs), held(n, a.cw);
+    }
     // units < 2^31 (launch_mmse_rank1) and rows <= units + 15: unit and frame indices fit 32 bits
-    const uint32_t units = (uint32_t)(SPLIT ? a.n * a.nblk : a.n);
-    const uint32_t rows = gridDim.x * 16u;
-    uint32_t g = blockIdx.x * 16u + (threadIdx.x >> 4);
+    const uint32_t units = (uint32_t)(SPLIT ? n * a.nblk : n);
+    const uint32_t rows = gridDim.x * rpw;
+    uint32_t g = blockIdx.x * rpw + (threadIdx.x >> 4);
     if (g >= units) return;   // whole 16-lane rows: the DPP sums stay inside a live row
     const bool cwg = !SHARED && a.cw != nullptr;
-    const double ac = st->acoef;
-    const uint64_t xm = st->xmask;
+    double ac;     // State::acoef, State::xmask and (off NOISE) State::bcoef: scalar loads through st,
+    uint64_t xm;   // needed only by the arithmetic
+    auto scalars = [&](double &b) __attribute__((always_inline)) {
+        ac = st->acoef;
+        xm = st->xmask;
+        if (!NOISE) b = st->bcoef;
+    };
     const double2 zero = make_double2(0.0, 0.0);
     // i, hidden from loop-invariant code motion: the per-lane parts of the addresses (a.tx + 16 i, ...) are
     // three VALU instructions to form again and would otherwise each hold a register pair across the loop
@@ -174,27 +204,56 @@ __global__ __launch_bounds__(256, R1_WG_PER_CU) void mmse_rank1_kernel(const Sta
     // u, w and p of the unit whose u row starts at cb, loaded like tx / rx: zero past subcarrier 52
     auto factors = [&](int64_t cb, double2(&u)[4], double2(&w)[4], double2(&p)[4]) __attribute__((always_inline)) {
         const int64_t ub = cb + i;
+        const bool live = i < NSC - 48;
+        if (SHARED) {
 #pragma unroll
-        for (int m = 0; m < 3; ++m) {
-            u[m] = ld2(a.cu, ub + 16 * m);
-            w[m] = cwg ? ld2(a.cw, ub + 16 * m) : cconj(u[m]);
-        }
-        u[3] = zero;
-        w[3] = zero;
-        if (i < NSC - 48) {
-            u[3] = ld2(a.cu, ub + 48);
-            w[3] = cwg ? ld2(a.cw, ub + 48) : cconj(u[3]);
+            for (int m = 0; m < 3; ++m) {
+                u[m] = ld2(a.cu, ub + 16 * m);
+                w[m] = cconj(u[m]);
+            }
+            u[3] = zero;
+            w[3] = zero;
+            if (live) {
+                u[3] = ld2(a.cu, ub + 48);
+                w[3] = cconj(u[3]);
+            }
+        } else {
+            // a unit's own u (and given w): every load is issued before the first conj(u) -- formed beside
+            // its load, each sign flip under the run-time cwg waited for all loads so far, four round trips
+#pragma unroll
+            for (int m = 0; m < 3; ++m) u[m] = ld2(a.cu, ub + 16 * m);
+            u[3] = zero;
+            if (live) u[3] = ld2(a.cu, ub + 48);
+            if (cwg) {
+#pragma unroll
+                for (int m = 0; m < 3; ++m) w[m] = ld2(a.cw, ub + 16 * m);
+                w[3] = zero;
+                if (live) w[3] = ld2(a.cw, ub + 48);
+            } else {
+#pragma unroll
+                for (int m = 0; m < 3; ++m) w[m] = cconj(u[m]);
+                w[3] = live ? cconj(u[3]) : zero;
+            }
         }
 #pragma unroll
         for (int m = 0; m < 4; ++m) p[m] = rank1_p(u[m], w[m], cwg);
     };
     double2 u[4], w[4], p[4];
+    double2 xc[4], rc[4], xn[4], rn[4];
+    double bc = 0.0, bn;   // NOISE: b is the unit's own, loaded by fetch
+    // The scalar loads through st are issued here and waited for at their first use, behind the vector loads
+    // (after fetch's asm they would no longer be provably unclobbered, and would become vector loads)
+    scalars(bc);
+    // LF: the first unit's tx / rx loads (and b) lead and the shared u follows -- every load of the wave is in
+    // flight before the first wait of the arithmetic
+    if (LF) fetch(g, xc, rc, bc);
     if (SHARED) factors(0, u, w, p);
-    // One trip: unit g from (xc, rc, bc) -- loaded here without prefetch -- while unit g + rows loads into
-    // (xn, rn, bn).  False after the row's last unit; otherwise g has moved on.
+    bn = bc;
+    // One trip: unit g from (xc, rc, bc) -- loaded by the caller, or here without PF and LF -- while unit
+    // g + rows loads into (xn, rn, bn).  False after the row's last unit; otherwise g has moved on.
     auto trip = [&](double2(&xc)[4], double2(&rc)[4], double &bc, double2(&xn)[4], double2(&rn)[4], double &bn)
                     __attribute__((always_inline)) {
-        if (!PF) fetch(g, xc, rc, bc);
+        if (!PF && !LF) fetch(g, xc, rc, bc);
         const uint32_t f = frame_of(g);
         if (!SHARED) factors((int64_t)f * a.cs, u, w, p);
         const bool more = g + rows < units;
@@ -230,15 +289,14 @@ __global__ __launch_bounds__(256, R1_WG_PER_CU) void mmse_rank1_kernel(const Sta
         g += rows;
         return more;
     };
-    double2 xc[4], rc[4], xn[4], rn[4];
-    double bc = st->bcoef, bn = bc;
     if (!PF) {
-        while (trip(xc, rc, bc, xn, rn, bn)) {}
+        while (trip(xc, rc, bc, xn, rn, bn))
+            if (LF) fetch(g, xc, rc, bc);
         return;
     }
     // The row's first trip stands apart from the loop, so that every later trip starts in one state, whichever
     // way it was reached: its unit's loads issued a whole trip ago, with only the last trip's stores behind them
-    fetch(g, xc, rc, bc);
+    if (!LF) fetch(g, xc, rc, bc);
     bool more = trip(xc, rc, bc, xn, rn, bn);
     while (more) {
         bc = bn;
@@ -253,30 +311,35 @@ __global__ __launch_bounds__(256, R1_WG_PER_CU) void mmse_rank1_kernel(const Sta
 
 int rank1_rows_per_sweep(int cus) { return (cus > 0 ? cus : 256) * R1_WG_PER_CU * 16; }
 
+// The launch of one call: grid, workgroup size (256, 128 or 64 threads: 16, 8 or 4 rows) and whether rows loop
+struct R1Shape {
+    dim3 g, b;
+    bool pf;   // a looping shape: the prefetching build where r1_prefetch allows
+};
+
 template <int POL, bool NOISE, bool SHARED>
-static void launch_r1_split(const State *st, const SolveArgs &a, bool pf, dim3 g, hipStream_t s)
+static void launch_r1_split(const State *st, const SolveArgs &a, const R1Shape &h, hipStream_t s)
 {
-    const dim3 b(256);
     if constexpr (r1_prefetch(NOISE, SHARED)) {
-        if (pf) {
-            if (a.split) hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, true, true>), g, b, 0, s, st, a);
-            else hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, false, true>), g, b, 0, s, st, a);
+        if (h.pf) {
+            if (a.split) hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, true, true>), h.g, h.b, 0, s, st, a);
+            else hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, false, true>), h.g, h.b, 0, s, st, a);
             return;
         }
     }
-    if (a.split) hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, true, false>), g, b, 0, s, st, a);
-    else hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, false, false>), g, b, 0, s, st, a);
+    if (a.split) hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, true, false>), h.g, h.b, 0, s, st, a);
+    else hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, false, false>), h.g, h.b, 0, s, st, a);
 }
 template <int POL>
-static void launch_r1_pol(const State *st, const SolveArgs &a, bool pf, dim3 g, hipStream_t s)
+static void launch_r1_pol(const State *st, const SolveArgs &a, const R1Shape &h, hipStream_t s)
 {
     const bool shared = a.cs == 0 && !a.cw;
     if (a.ow2) {
-        if (shared) launch_r1_split<POL, true, true>(st, a, pf, g, s);
-        else launch_r1_split<POL, true, false>(st, a, pf, g, s);
+        if (shared) launch_r1_split<POL, true, true>(st, a, h, s);
+        else launch_r1_split<POL, true, false>(st, a, h, s);
     } else {
-        if (shared) launch_r1_split<POL, false, true>(st, a, pf, g, s);
-        else launch_r1_split<POL, false, false>(st, a, pf, g, s);
+        if (shared) launch_r1_split<POL, false, true>(st, a, h, s);
+        else launch_r1_split<POL, false, false>(st, a, h, s);
     }
 }
 
@@ -289,19 +352,21 @@ int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, int cus, voi
     if (a.ow2 && a.cw) return WCE_EINVAL;   // per-frame noise: TEXTBOOK only (check_route_facts), so w = conj(u)
     const int64_t units = a.split ? a.n * a.nblk : a.n;
     if (units > 0x7fffffffll) return WCE_EINVAL;
-    // the launch shape and the A/B cache policies (WCE_VARIANT_R1 = 3..7) are this launcher's alone:
+    // the launch shape and the A/B cache policies (WCE_VARIANT_R1 = 3..10) are this launcher's alone:
     // to the route planner they are the closed form
     const int shape = variant_value(WCE_VARIANT_R1);
-    int64_t wgs = (units + 15) / 16;   // one unit per row: the default, and what a batch below one sweep gets anyway
+    const int rpw = shape == 8 ? 4 : shape == 9 ? 8 : 16;   // rows per workgroup: the kernel reads blockDim.x
+    int64_t wgs = (units + rpw - 1) / rpw;   // one unit per row: the default, and what a batch below one sweep gets anyway
     const bool looping = shape == 4 || shape == 7;
     const int64_t cap = shape == 4 ? 3 : shape == 7 ? rank1_rows_per_sweep(cus) / 16 : wgs;
     if (wgs > cap) wgs = cap;
-    const dim3 g((unsigned)wgs);
+    const R1Shape h{dim3((unsigned)wgs), dim3(16u * rpw), looping};
     hipStream_t s = (hipStream_t)stream;
-    if (nt) launch_r1_pol<R1_POL_NT>(st, a, looping, g, s);
-    else if (shape == 5) launch_r1_pol<R1_POL_NT_STORES>(st, a, looping, g, s);
-    else if (shape == 6) launch_r1_pol<R1_POL_NT_LOADS>(st, a, looping, g, s);
-    else launch_r1_pol<R1_POL_DEFAULT>(st, a, looping, g, s);
+    if (nt) launch_r1_pol<R1_POL_NT>(st, a, h, s);
+    else if (shape == 5) launch_r1_pol<R1_POL_NT_STORES>(st, a, h, s);
+    else if (shape == 6) launch_r1_pol<R1_POL_NT_LOADS>(st, a, h, s);
+    else if (shape == 10) launch_r1_pol<R1_POL_U_FIRST>(st, a, h, s);
+    else launch_r1_pol<R1_POL_DEFAULT>(st, a, h, s);
     return hipGetLastError() == hipSuccess ? WCE_OK : WCE_EHIP;
 }
 

@@ -60,7 +60,7 @@ int wce_debug_set_flat_chunk(long long frames);
  * also asks for LS outputs or equalization runs the LS pass, then this kernel;
  * 1 = the 53 x 53 factorisation, mmse_solve_fc_kernel, one wave per (frame,
  * block), and with LS outputs the fused mmse_solve_ls_kernel; 2 = the closed
- * form with nontemporal loads and stores; 3..7 are launch shapes and cache
+ * form with nontemporal loads and stores; 3..10 are launch shapes and cache
  * policies of the closed form, the same route as 0 and read by its launcher
  * alone: 3 = one unit per 16-lane row, the grid covers the batch, so no row
  * loops and nothing is prefetched -- the shape 0 launches too; 4 = the grid
@@ -68,10 +68,13 @@ int wce_debug_set_flat_chunk(long long frames);
  * many ragged loop trips; 5 = nontemporal stores with default loads; 6 =
  * nontemporal loads with default stores; 7 = the persistent grid, at most
  * wce_debug_rank1_rows_per_sweep rows that loop over the batch with the next
- * unit's loads in flight -- built, tested and measured no faster than 0).
+ * unit's loads in flight -- built, tested and measured no faster than 0;
+ * 8 / 9 = the default grid in workgroups of 64 / 128 threads; 10 = the
+ * default grid with the previous prologue, the shared u waited for before the
+ * first tx / rx load).
  * Process-wide; the variants of which 0, 1, 2, 4 give bit-identical results,
  * which 3's kernels sum in different orders and agree to rounding (tests
- * check both); which 5's 0 and 2..7 are bit-identical, 0 and 1 agree to ~1e-11
+ * check both); which 5's 0 and 2..10 are bit-identical, 0 and 1 agree to ~1e-11
  * (both within 1e-10 of the long double closed form).  (Round 4 retired ls_flat_kernel -- which 1 = 0, 1 -- and the
  * REF frame tiles -- which 0 = 1.) */
 int wce_debug_set_variant(int which, int value);

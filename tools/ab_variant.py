@@ -4,7 +4,8 @@ timing per launch, outputs compared bit for bit across variants.
 usage: python tools/ab_variant.py {ref,ls,dense,rank1} [--variants 0 1] [--rounds 5] [--reps 20]
 rank1: the TEXTBOOK headline under WCE_VARIANT_R1 (0 closed form, 1 factorisation, 2 closed form, nontemporal,
 3 one unit per row like 0, 4 three workgroups, 5 nontemporal stores, 6 nontemporal loads, 7 persistent grid with
-prefetch); 0 and 2..7 are bit-identical, 1 agrees to rounding."""
+prefetch, 8 / 9 workgroups of 64 / 128 threads, 10 the previous prologue: u before tx / rx); 0 and 2..10 are
+bit-identical, 1 agrees to rounding."""
 import argparse
 import importlib
 import os
