@@ -28,6 +28,8 @@ struct wce_ctx {
     int cov_taps = 0;           // State::cov_taps | State::taps_contig << 1 (diagonal Rhh: the tap-domain forms)
     int cov_path = 0;           // wce_debug_set_cov_path: 0 auto, 1 dense, 2 low-rank
     int cus = 0;                // CU count of `device`, read once in wce_ctx_create_empty (launch shapes; never on the launch path)
+    bool r1_plain = false;      // State::acoef == 1.0 and a full State::xmask (every TEXTBOOK state): the rank-1 kernel's
+                                // build without mask and scale.  Set with `mode`, wherever the state comes from
     bool cm_on = false;         // State::cm_on: a constant-modulus operator is loaded (wce_ctx_set_modulus)
     bool cm_use = true;         // wce_debug_set_cm: A/B switch of that path
     std::vector<wce_complex> rhh;   // WCE_MMSE_COV ctx built here: the caller's Rhh (for wce_ctx_set_modulus)
@@ -49,6 +51,9 @@ static constexpr int64_t WS_LD = 64;   // row stride (complex) of the workspace 
 static constexpr int64_t WS_ARRAYS = 5;
 
 static thread_local std::string g_err;
+
+// mmse_rank1_kernel's PLAIN build may run: X is the whole tx block and a = 1 (wce_state.cpp, TEXTBOOK)
+static bool state_r1_plain(const State *st) { return st->acoef == 1.0 && st->xmask == (1ull << wce::NSC) - 1; }
 
 static int fail(int code, const char *what)
 {
@@ -141,6 +146,7 @@ int wce_ctx_create(wce_ctx **out, int device, const wce_complex *tx_pre, const w
     if (rc) { wce_ctx_destroy(c); return fail(rc, "state build"); }
     c->has_host = true;
     c->mode = mode;
+    c->r1_plain = state_r1_plain(&c->host);
     DeviceGuard g(device);
     hipError_t e = hipMemcpy(c->d_state, &c->host, sizeof(State), hipMemcpyHostToDevice);
     if (e != hipSuccess) { wce_ctx_destroy(c); return hipfail(e, "upload state"); }
@@ -211,6 +217,7 @@ int wce_ctx_mark_ready(wce_ctx *c)
         c->rhh.clear();
     }
     c->mode = h->mode;
+    c->r1_plain = state_r1_plain(h.get());
     c->cov_rank = h->cov_rank;
     c->cov_k0 = h->cov_k0;
     c->cov_taps = (h->cov_taps ? 1 : 0) | (h->taps_contig ? 2 : 0);
@@ -232,6 +239,7 @@ int wce_ctx_load_state(wce_ctx *c, const void *host_state, size_t bytes)
         c->rhh.clear();
     }
     c->mode = st->mode;
+    c->r1_plain = state_r1_plain(st);
     c->cov_k0 = st->cov_k0;
     c->cov_rank = st->cov_rank;
     c->cov_taps = (st->cov_taps ? 1 : 0) | (st->taps_contig ? 2 : 0);
@@ -694,8 +702,8 @@ static int estimate_impl(wce_ctx *c, const wce_frames *in, const wce_outputs *ou
         break;
     case wce::SolveStep::RefPilots: rc = wce::launch_mmse_ref_pilots(st, sa, stream); break;
     case wce::SolveStep::RefLsElem: rc = wce::launch_ref_ls_elem(st, sa, la, false, stream); break;
-    case wce::SolveStep::Closed: rc = wce::launch_mmse_rank1(st, sa, false, c->cus, stream); break;
-    case wce::SolveStep::ClosedNt: rc = wce::launch_mmse_rank1(st, sa, true, c->cus, stream); break;
+    case wce::SolveStep::Closed: rc = wce::launch_mmse_rank1(st, sa, false, c->cus, c->r1_plain, stream); break;
+    case wce::SolveStep::ClosedNt: rc = wce::launch_mmse_rank1(st, sa, true, c->cus, c->r1_plain, stream); break;
     case wce::SolveStep::Factor: rc = wce::launch_mmse_factor(st, sa, r.form, stream); break;
     case wce::SolveStep::Fused: rc = wce::launch_mmse_solve_ls(st, sa, la, r.form, stream); break;
     }

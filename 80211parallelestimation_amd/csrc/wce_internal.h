@@ -253,8 +253,10 @@ int launch_mmse_factor(const State *st, const SolveArgs &a, SolveForm form, void
 // the closed-form bordered rank-1 solve (wce_rank1.hip); nt: nontemporal loads and stores;
 // a.ow2 set: its per-frame-noise build; cus: the device's CU count, read when the context was
 // made (never on this path: plans replay it), which sizes the persistent grid.
-// WCE_VARIANT_R1 = 3..10 pick the launch shape, cache policy and prologue here
-int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, int cus, void *stream);
+// plain: State::acoef is 1.0 and State::xmask is full (every TEXTBOOK state) -- a fact the context caches
+// when it takes its State, like cus; the default build then neither reads nor applies them.
+// WCE_VARIANT_R1 = 3..12 pick the launch shape, cache policy, prologue and build here
+int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, int cus, bool plain, void *stream);
 // units one sweep of its persistent grid covers on a device of `cus` CUs (wce_debug_rank1_rows_per_sweep)
 int rank1_rows_per_sweep(int cus);
 // the same factorisation + LS family + equalization of each frame in one launch (C semantics, one block)
@@ -331,7 +333,7 @@ constexpr int WCE_VARIANT_R1 = 5;      // PS_MMSE with a rank-1 covariance (TEXT
                                       // and the fused mmse_solve_ls_kernel), 2 = the closed form with
                                       // nontemporal loads and stores; 0 and 2 bit-identical, 0 and 1 agree to
                                       // ~1e-11 (each within 1e-10 of the long double answer).
-                                      // 3..10 are the closed form to the route planner and are read by
+                                      // 3..12 are the closed form to the route planner and are read by
                                       // launch_mmse_rank1 alone: 3 = one unit per 16-lane row, the grid covers
                                       // the batch -- what 0 launches too, since the persistent grid measured
                                       // no faster (DESIGN s6), 4 = the grid capped at 3 workgroups (48 rows
@@ -341,8 +343,13 @@ constexpr int WCE_VARIANT_R1 = 5;      // PS_MMSE with a rank-1 covariance (TEXT
                                       // at most 4 workgroups per CU, rows loop with the next unit's loads in
                                       // flight, 8 / 9 = the default grid in workgroups of 64 / 128 threads
                                       // (4 / 8 rows), 10 = the default grid with the previous prologue (u and
-                                      // the State scalars waited for before the first tx / rx load); all
-                                      // bit-identical to 0
+                                      // the State scalars waited for before the first tx / rx load), 11 = the
+                                      // general build under the default policy: it reads State::acoef and
+                                      // State::xmask and applies them, where 0 on a State with a = 1 and a full
+                                      // mask (every TEXTBOOK State) runs the build without them, 12 = that
+                                      // build with tx and rx loads alternating and the shared u last, where 0
+                                      // issues tx, u, rx row by row; all bit-identical to 0.  2, 5, 6 and 10
+                                      // run the general build whatever the State
 constexpr int WCE_VARIANT_COUNT = 6;
 int variant_value(int which);
 int set_variant(int which, int value);

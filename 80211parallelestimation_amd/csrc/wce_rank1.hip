@@ -36,9 +36,16 @@
 // unit's sums) is built and tested but measured no faster: WCE_VARIANT_R1 = 7,
 // DESIGN s6.
 //
+// a = 1 and a full State::xmask (every TEXTBOOK State; the context caches the fact with the State's mode) run a
+// build without the mask selects and the scale: X is the tx block as loaded.  REF (a = 0, the four pilots) and
+// any other State keep the general build, which WCE_VARIANT_R1 = 11 also runs for the same-binary A/B.  The two
+// give the same bits.  Fused products and one reciprocal per denominator (a third fewer VALU instructions
+// again, and other bits) were built and measured no faster: the arithmetic below is unchanged (DESIGN s6).
+//
 // A wave's prologue is one scalar round trip (the kernel arguments, a.n among them),
-// the bounds test, and then every vector load of its first unit: tx / rx first, the
-// shared u behind them, one wait chain in front of the arithmetic.
+// the bounds test, and then every vector load of its first unit, one wait chain in front
+// of the arithmetic.  The headline's order is tx, the shared u, rx, each row's loads together;
+// the other builds alternate tx and rx and load u behind them.
 #include "wce_internal.h"
 #include "wce_device.h"
 
@@ -69,6 +76,7 @@ __device__ __forceinline__ double2 rank1_p(double2 u, double2 w, bool cwg)
 // in x, r (rx), u, w and p (rank1_p); entries past subcarrier 52 (and x off
 // State::xmask) are zero.  cwg: w was given (SolveArgs::cw) -- g may be complex;
 // otherwise w = conj(u) and g = a sum |x|^2 |u|^2 is real.  Every lane returns the same bits.
+template <bool PLAIN>
 __device__ __forceinline__ double2 rank1_s(const double2 (&x)[4], const double2 (&r)[4], const double2 (&u)[4],
                                            const double2 (&w)[4], const double2 (&p)[4], bool cwg, double ac,
                                            double bc)
@@ -77,7 +85,8 @@ __device__ __forceinline__ double2 rank1_s(const double2 (&x)[4], const double2 
     double2 g = make_double2(0.0, 0.0), q = g;
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-        const double ax2 = ac * (x[m].x * x[m].x + x[m].y * x[m].y);
+        const double x2 = x[m].x * x[m].x + x[m].y * x[m].y;
+        const double ax2 = PLAIN ? x2 : ac * x2;
         const double2 gk = make_double2(ax2 * p[m].x, ax2 * p[m].y);    // be_k al_k = a |x_k|^2 w_k u_k
         const double2 qk = r1_mul(r1_mul(w[m], cconj(x[m])), r[m]);     // be_k rx_k
         g = m ? r1_add(g, gk) : gk;
@@ -97,7 +106,7 @@ __device__ __forceinline__ double2 rank1_s(const double2 (&x)[4], const double2 
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
         const double2 xu = r1_mul(x[m], u[m]);
-        const double2 at = r1_mul(make_double2(ac * xu.x, ac * xu.y), t);   // al_k t
+        const double2 at = r1_mul(PLAIN ? xu : make_double2(ac * xu.x, ac * xu.y), t);   // al_k t
         const double2 rho = make_double2(r[m].x - at.x, r[m].y - at.y);
         const double ti = 2.0 * x[m].y;                                      // x - conj x = (0, 2 Im x)
         const double2 ck = r1_mul(w[m], make_double2(-(ti * rho.y), ti * rho.x));
@@ -115,6 +124,12 @@ constexpr int R1_POL_DEFAULT = 0, R1_POL_NT = 1, R1_POL_NT_STORES = 2, R1_POL_NT
 // the default cache policy behind the previous prologue (A/B, WCE_VARIANT_R1 = 10): u and the State scalars
 // are loaded and waited for before the first tx / rx load is issued
 constexpr int R1_POL_U_FIRST = 4;
+// the default cache policy with the loads issued row by row: a unit's four tx loads, the shared u, its four rx
+// loads -- where R1_POL_DEFAULT alternates tx and rx and puts u last.  What the shared-u launches of the build
+// without mask and scale run (WCE_VARIANT_R1 = 12 keeps them on R1_POL_DEFAULT for the A/B): 0.35 to 0.4 us
+// less at 65,536 frames in every same-binary A/B, nothing past the Infinity Cache; moving g and the other
+// sums that need tx and u alone ahead of the rx wait as well measured the same as the order alone (DESIGN s6)
+constexpr int R1_POL_TX_FIRST = 5;
 
 // One 16-lane row per unit g = frame (or, SPLIT, frame * nblk + block): H = u s
 // to row f of a.w, or (SPLIT, MATLAB averaging) s_b to a.dots[g] for
@@ -136,14 +151,20 @@ constexpr int R1_POL_U_FIRST = 4;
 // instantiations that hold more (ow2, a unit's own u and w) would spill, and load each
 // unit in its own trip whatever the shape.
 constexpr bool r1_prefetch(bool noise, bool shared) { return shared && !noise; }
+// PLAIN (launch_mmse_rank1's `plain`): State::acoef is 1.0 and State::xmask is full, a fact of the State fixed
+// when the context took it.  X is the loaded tx block as it is, a drops out of al and g, and neither
+// State::acoef nor State::xmask is read.  Multiplying by 1.0 and selecting under a full mask change no bit:
+// the build's results are those of the general one.
 
-template <int POL, bool NOISE, bool SHARED, bool SPLIT, bool PF>
+template <int POL, bool NOISE, bool SHARED, bool SPLIT, bool PF, bool PLAIN>
 __global__ __launch_bounds__(256, R1_WG_PER_CU) void mmse_rank1_kernel(const State *__restrict__ st, SolveArgs a)
 {
     static_assert(!PF || r1_prefetch(NOISE, SHARED), "this instantiation has no registers for a second unit");
     constexpr bool NTL = POL == R1_POL_NT || POL == R1_POL_NT_LOADS;
     constexpr bool NTS = POL == R1_POL_NT || POL == R1_POL_NT_STORES;
     constexpr bool LF = POL != R1_POL_U_FIRST;   // loads first
+    constexpr bool TXF = POL == R1_POL_TX_FIRST;
+    static_assert(!TXF || (SHARED && PLAIN), "the tx-first order is built for the shared-u builds without mask and scale");
     const int i = threadIdx.x & 15;
     const uint32_t rpw = blockDim.x >> 4;   // rows per workgroup: 16, 8 or 4
     int64_t n = a.n;
@@ -169,8 +190,8 @@ __global__ __launch_bounds__(256, R1_WG_PER_CU) void mmse_rank1_kernel(const Sta
     double ac;     // State::acoef, State::xmask and (off NOISE) State::bcoef: scalar loads through st,
     uint64_t xm;   // needed only by the arithmetic
     auto scalars = [&](double &b) __attribute__((always_inline)) {
-        ac = st->acoef;
-        xm = st->xmask;
+        ac = PLAIN ? 1.0 : st->acoef;
+        xm = PLAIN ? ~0ull : st->xmask;
         if (!NOISE) b = st->bcoef;
     };
     const double2 zero = make_double2(0.0, 0.0);
@@ -184,10 +205,27 @@ __global__ __launch_bounds__(256, R1_WG_PER_CU) void mmse_rank1_kernel(const Sta
     // the tx / rx loads of unit gu and (NOISE) its b, all independent: one memory round trip.  Subcarriers
     // 48..52 (m = 3) are loaded by lanes 0..4 alone, at the address of the other three plus an immediate,
     // and are zero in the other lanes
-    auto fetch = [&](uint32_t gu, double2(&xl)[4], double2(&rl)[4], double &bc) __attribute__((always_inline)) {
+    // TXF: tx whole, then rx (`part` 1 / 2: one side only, so that the shared u can stand between them)
+    auto fetch = [&](uint32_t gu, double2(&xl)[4], double2(&rl)[4], double &bc, int part = 0) __attribute__((always_inline)) {
         const uint32_t f = frame_of(gu);
         const int b = SPLIT ? (int)(gu - f * (uint32_t)a.nblk) : 0;
         const int64_t base = (int64_t)f * a.fs + (int64_t)(a.blk + b) * a.bs + lane_again(i);
+        if (TXF) {
+            if (part != 2) {
+#pragma unroll
+                for (int m = 0; m < 3; ++m) xl[m] = ld2(a.tx, base + 16 * m);
+                xl[3] = zero;
+                if (i < NSC - 48) xl[3] = ld2(a.tx, base + 48);
+            }
+            if (part != 1) {
+#pragma unroll
+                for (int m = 0; m < 3; ++m) rl[m] = ld2(a.rx, base + 16 * m);
+                rl[3] = zero;
+                if (i < NSC - 48) rl[3] = ld2(a.rx, base + 48);
+                if (NOISE) bc = a.ow2[f];
+            }
+            return;
+        }
 #pragma unroll
         for (int m = 0; m < 3; ++m) {
             xl[m] = NTL ? ld2_nt(a.tx, base + 16 * m) : ld2(a.tx, base + 16 * m);
@@ -246,8 +284,24 @@ __global__ __launch_bounds__(256, R1_WG_PER_CU) void mmse_rank1_kernel(const Sta
     scalars(bc);
     // LF: the first unit's tx / rx loads (and b) lead and the shared u follows -- every load of the wave is in
     // flight before the first wait of the arithmetic
-    if (LF) fetch(g, xc, rc, bc);
-    if (SHARED) factors(0, u, w, p);
+    if (TXF) {
+        // tx, the shared u, rx: loads only, and conj(u) and |u|^2 behind the last of them -- a sign flip beside
+        // the lane-masked u load would wait for tx and u inside its branch, ahead of the first rx load
+        fetch(g, xc, rc, bc, 1);
+#pragma unroll
+        for (int m = 0; m < 3; ++m) u[m] = ld2(a.cu, i + 16 * m);
+        u[3] = zero;
+        if (i < NSC - 48) u[3] = ld2(a.cu, i + 48);
+        fetch(g, xc, rc, bc, 2);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            w[m] = m < 3 || i < NSC - 48 ? cconj(u[m]) : zero;
+            p[m] = rank1_p(u[m], w[m], cwg);
+        }
+    } else {
+        if (LF) fetch(g, xc, rc, bc);
+        if (SHARED) factors(0, u, w, p);
+    }
     bn = bc;
     // One trip: unit g from (xc, rc, bc) -- loaded by the caller, or here without PF and LF -- while unit
     // g + rows loads into (xn, rn, bn).  False after the row's last unit; otherwise g has moved on.
@@ -261,7 +315,7 @@ __global__ __launch_bounds__(256, R1_WG_PER_CU) void mmse_rank1_kernel(const Sta
         double2 x[4];
 #pragma unroll
         for (int m = 0; m < 4; ++m)   // subcarriers off State::xmask do not enter X
-            x[m] = (xm >> ((i + 16 * m) & 63)) & 1ull ? xc[m] : zero;
+            x[m] = PLAIN || ((xm >> ((i + 16 * m) & 63)) & 1ull) ? xc[m] : zero;
         // PF: |u|^2 is formed again in every trip, from a u hidden from loop-invariant code motion.  Held
         // across the trips it is the 8 registers that tip this build into scratch (DESIGN s6); u itself stays
         double2 pl[4];
@@ -271,7 +325,7 @@ __global__ __launch_bounds__(256, R1_WG_PER_CU) void mmse_rank1_kernel(const Sta
             if (PF) asm volatile("" : "+v"(um.x), "+v"(um.y));
             pl[m] = PF ? rank1_p(um, w[m], cwg) : p[m];
         }
-        double2 s = rank1_s(x, rc, u, w, pl, cwg, ac, bc);
+        double2 s = rank1_s<PLAIN>(x, rc, u, w, pl, cwg, ac, bc);
         if (NOISE && !(bc > 0.0 && bc < __builtin_inf())) s = make_double2(__builtin_nan(""), __builtin_nan(""));
         if (SPLIT) {
             if (i == 0) st2(a.dots, g, s);
@@ -317,33 +371,36 @@ struct R1Shape {
     bool pf;   // a looping shape: the prefetching build where r1_prefetch allows
 };
 
-template <int POL, bool NOISE, bool SHARED>
+template <int POL, bool NOISE, bool SHARED, bool PLAIN>
 static void launch_r1_split(const State *st, const SolveArgs &a, const R1Shape &h, hipStream_t s)
 {
     if constexpr (r1_prefetch(NOISE, SHARED)) {
         if (h.pf) {
-            if (a.split) hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, true, true>), h.g, h.b, 0, s, st, a);
-            else hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, false, true>), h.g, h.b, 0, s, st, a);
+            if (a.split) hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, true, true, PLAIN>), h.g, h.b, 0, s, st, a);
+            else hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, false, true, PLAIN>), h.g, h.b, 0, s, st, a);
             return;
         }
     }
-    if (a.split) hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, true, false>), h.g, h.b, 0, s, st, a);
-    else hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, false, false>), h.g, h.b, 0, s, st, a);
+    if (a.split) hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, true, false, PLAIN>), h.g, h.b, 0, s, st, a);
+    else hipLaunchKernelGGL((mmse_rank1_kernel<POL, NOISE, SHARED, false, false, PLAIN>), h.g, h.b, 0, s, st, a);
 }
-template <int POL>
+template <int POL, bool PLAIN = false>
 static void launch_r1_pol(const State *st, const SolveArgs &a, const R1Shape &h, hipStream_t s)
 {
     const bool shared = a.cs == 0 && !a.cw;
-    if (a.ow2) {
-        if (shared) launch_r1_split<POL, true, true>(st, a, h, s);
-        else launch_r1_split<POL, true, false>(st, a, h, s);
+    if constexpr (POL == R1_POL_TX_FIRST) {   // the shared-u builds only (launch_mmse_rank1)
+        if (a.ow2) launch_r1_split<POL, true, true, PLAIN>(st, a, h, s);
+        else launch_r1_split<POL, false, true, PLAIN>(st, a, h, s);
+    } else if (a.ow2) {
+        if (shared) launch_r1_split<POL, true, true, PLAIN>(st, a, h, s);
+        else launch_r1_split<POL, true, false, PLAIN>(st, a, h, s);
     } else {
-        if (shared) launch_r1_split<POL, false, true>(st, a, h, s);
-        else launch_r1_split<POL, false, false>(st, a, h, s);
+        if (shared) launch_r1_split<POL, false, true, PLAIN>(st, a, h, s);
+        else launch_r1_split<POL, false, false, PLAIN>(st, a, h, s);
     }
 }
 
-int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, int cus, void *stream)
+int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, int cus, bool plain, void *stream)
 {
     if (!a.cu) return WCE_EINVAL;
     if (a.split ? !a.dots : !a.w) return WCE_EINVAL;
@@ -352,8 +409,10 @@ int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, int cus, voi
     if (a.ow2 && a.cw) return WCE_EINVAL;   // per-frame noise: TEXTBOOK only (check_route_facts), so w = conj(u)
     const int64_t units = a.split ? a.n * a.nblk : a.n;
     if (units > 0x7fffffffll) return WCE_EINVAL;
-    // the launch shape and the A/B cache policies (WCE_VARIANT_R1 = 3..10) are this launcher's alone:
-    // to the route planner they are the closed form
+    // the launch shape and the A/B builds (WCE_VARIANT_R1 = 3..12) are this launcher's alone: to the route
+    // planner they are the closed form.  The build without mask and scale exists under the default cache
+    // policy only (with a shared u: loads row by row, unless 12): the A/B policies (2, 5, 6, 10) run the
+    // general build whatever the State, and 11 runs it under the default policy
     const int shape = variant_value(WCE_VARIANT_R1);
     const int rpw = shape == 8 ? 4 : shape == 9 ? 8 : 16;   // rows per workgroup: the kernel reads blockDim.x
     int64_t wgs = (units + rpw - 1) / rpw;   // one unit per row: the default, and what a batch below one sweep gets anyway
@@ -366,7 +425,9 @@ int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, int cus, voi
     else if (shape == 5) launch_r1_pol<R1_POL_NT_STORES>(st, a, h, s);
     else if (shape == 6) launch_r1_pol<R1_POL_NT_LOADS>(st, a, h, s);
     else if (shape == 10) launch_r1_pol<R1_POL_U_FIRST>(st, a, h, s);
-    else launch_r1_pol<R1_POL_DEFAULT>(st, a, h, s);
+    else if (!plain || shape == 11) launch_r1_pol<R1_POL_DEFAULT>(st, a, h, s);
+    else if (a.cs == 0 && !a.cw && shape != 12) launch_r1_pol<R1_POL_TX_FIRST, true>(st, a, h, s);
+    else launch_r1_pol<R1_POL_DEFAULT, true>(st, a, h, s);
     return hipGetLastError() == hipSuccess ? WCE_OK : WCE_EHIP;
 }
 

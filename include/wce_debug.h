@@ -60,8 +60,8 @@ int wce_debug_set_flat_chunk(long long frames);
  * also asks for LS outputs or equalization runs the LS pass, then this kernel;
  * 1 = the 53 x 53 factorisation, mmse_solve_fc_kernel, one wave per (frame,
  * block), and with LS outputs the fused mmse_solve_ls_kernel; 2 = the closed
- * form with nontemporal loads and stores; 3..10 are launch shapes and cache
- * policies of the closed form, the same route as 0 and read by its launcher
+ * form with nontemporal loads and stores; 3..12 are launch shapes, cache
+ * policies and builds of the closed form, the same route as 0 and read by its launcher
  * alone: 3 = one unit per 16-lane row, the grid covers the batch, so no row
  * loops and nothing is prefetched -- the shape 0 launches too; 4 = the grid
  * capped at 3 workgroups, 48 rows per sweep, so a few hundred frames make
@@ -71,10 +71,14 @@ int wce_debug_set_flat_chunk(long long frames);
  * unit's loads in flight -- built, tested and measured no faster than 0;
  * 8 / 9 = the default grid in workgroups of 64 / 128 threads; 10 = the
  * default grid with the previous prologue, the shared u waited for before the
- * first tx / rx load).
+ * first tx / rx load); 11 = the general build under the default policy, which
+ * reads State::acoef and State::xmask and applies them -- on a State with
+ * a = 1 and a full mask (every TEXTBOOK State) 0 runs a build without them;
+ * 12 = that build with tx and rx loads alternating and the shared u last,
+ * where 0 issues tx, u and rx row by row).
  * Process-wide; the variants of which 0, 1, 2, 4 give bit-identical results,
  * which 3's kernels sum in different orders and agree to rounding (tests
- * check both); which 5's 0 and 2..10 are bit-identical, 0 and 1 agree to ~1e-11
+ * check both); which 5's 0 and 2..12 are bit-identical, 0 and 1 agree to ~1e-11
  * (both within 1e-10 of the long double closed form).  (Round 4 retired ls_flat_kernel -- which 1 = 0, 1 -- and the
  * REF frame tiles -- which 0 = 1.) */
 int wce_debug_set_variant(int which, int value);

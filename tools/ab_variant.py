@@ -4,7 +4,9 @@ timing per launch, outputs compared bit for bit across variants.
 usage: python tools/ab_variant.py {ref,ls,dense,rank1} [--variants 0 1] [--rounds 5] [--reps 20]
 rank1: the TEXTBOOK headline under WCE_VARIANT_R1 (0 closed form, 1 factorisation, 2 closed form, nontemporal,
 3 one unit per row like 0, 4 three workgroups, 5 nontemporal stores, 6 nontemporal loads, 7 persistent grid with
-prefetch, 8 / 9 workgroups of 64 / 128 threads, 10 the previous prologue: u before tx / rx); 0 and 2..10 are
+prefetch, 8 / 9 workgroups of 64 / 128 threads, 10 the previous prologue: u before tx / rx, 11 the general build
+that reads and applies State::acoef and State::xmask, 12 the build without them with tx / rx loads alternating
+and u last, where 0 loads tx, u, rx row by row); 0 and 2..12 are
 bit-identical, 1 agrees to rounding."""
 import argparse
 import importlib
@@ -111,7 +113,7 @@ def main():
     for v, ts in times.items():
         t = float(np.median(ts))
         print(f"{args.leg} variant {v}: median {t * 1e3:.1f} us  min {min(ts) * 1e3:.1f}  "
-              f"{alg * n / (t * 1e-3) / 1e12:.2f} TB/s {unit}  ({', '.join(f'{x * 1e3:.0f}' for x in ts)})")
+              f"{alg * n / (t * 1e-3) / 1e12:.2f} TB/s {unit}  ({', '.join(f'{x * 1e3:.2f}' for x in ts)})")
 
 
 if __name__ == "__main__":

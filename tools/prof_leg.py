@@ -4,8 +4,8 @@ workload for rocprofv3 --pmc passes (tools/pmc_legs.sh), so that a per-kernel
 average over the dispatches of a pass is an average over same-size launches.
 
 legs (bench.py field -> kernel, frames per launch):
-  headline   roofline            mmse_rank1_kernel<0, false, true, false, false>  65,536 (TEXTBOOK closed form, 16 lanes/frame:
-                                 default cache policy, no per-frame noise, shared u, not split, no prefetch)
+  headline   roofline            mmse_rank1_kernel<5, false, true, false, false, true>  65,536 (TEXTBOOK closed form, 16 lanes/frame:
+                                 loads row by row, no per-frame noise, shared u, not split, no prefetch, no mask and scale)
   apply      apply_kernel        apply_kernel                     65,536 (COV H = C W, persistent since round 5)
   cov_solve  cov_mode            mmse_solve_kernel<false>         65,536 (COV dense solve)
   ref        ref_mode.b1048576   mmse_ref_elem_kernel          1,048,576 (REF, main.c semantics)
@@ -34,7 +34,7 @@ sys.path.insert(0, REPO)
 N, NBLK = 53, 15
 
 LEGS = {
-    "headline": ("mmse_rank1_kernel<0, false, true, false, false>", 65536),   # the closed-form rank-1 solve (wce_rank1.hip)
+    "headline": ("mmse_rank1_kernel<5, false, true, false, false, true>", 65536),   # the closed-form rank-1 solve (wce_rank1.hip)
     "apply": ("apply_kernel", 65536),                # round 5: the streaming kernel at every size
     "apply1m": ("apply_kernel", 1 << 20),             # the same at configs[3]'s batch
     "cov_solve": ("mmse_solve_kernel<false>", 65536),
