@@ -1066,6 +1066,91 @@ int wce_demodulate(wce_ctx *c, const wce_frames *in, const wce_demod *p, const w
     return rc ? fail(rc, "demod launch") : WCE_OK;
 }
 
+// ---------------------------------------------------------------- decoding
+int wce_decode_info_bits(int32_t modulation, int32_t rate)
+{
+    const int T = wce::decode_info_bits(modulation, rate);
+    return T < 0 ? fail(WCE_EINVAL, "wce_decode_info_bits: unknown modulation or rate") : T;
+}
+
+// block stride >= row and, with more than one frame, frame stride >= 14 block strides + one row
+static bool strides_hold(int64_t n, int64_t fs, int64_t bs, int64_t row)
+{
+    return bs >= row && (n <= 1 || fs >= (wce::NBLK - 1) * bs + row);
+}
+
+int wce_soft_demap(wce_ctx *c, const wce_complex *eq, int64_t eq_frame_stride, int64_t eq_block_stride,
+                   const wce_demod *p, int64_t n, float *llr, int64_t llr_frame_stride, int64_t llr_block_stride,
+                   void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    if (!eq || !p || !llr) return fail(WCE_EINVAL, "wce_soft_demap: null eq, parameters or llr");
+    if (!p->h) return fail(WCE_EINVAL, "wce_soft_demap: h required");
+    if (p->h_stride < wce::NSC) return fail(WCE_EINVAL, "wce_soft_demap: h_stride < 53");
+    double K;
+    switch (p->modulation) {   // the doubles nearest to 1 / sqrt(1, 2, 10, 42), as wce_demodulate
+    case WCE_MOD_BPSK: K = 1.0; break;
+    case WCE_MOD_QPSK: K = 0.70710678118654752440; break;
+    case WCE_MOD_QAM16: K = 0.31622776601683793320; break;
+    case WCE_MOD_QAM64: K = 0.15430334996209191026; break;
+    default: return fail(WCE_EINVAL, "wce_soft_demap: unknown modulation");
+    }
+    if (!(p->scale > 0.0) || p->scale * 0.0 != 0.0) return fail(WCE_EINVAL, "wce_soft_demap: scale not positive and finite");
+    if (n < 0 || n > 0x7fffffffll) return fail(WCE_EINVAL, "wce_soft_demap: n_frames < 0 or > 2^31 - 1");
+    if (!strides_hold(n, eq_frame_stride, eq_block_stride, wce::NSC))
+        return fail(WCE_EINVAL, "wce_soft_demap: eq strides too small");
+    if (!strides_hold(n, llr_frame_stride, llr_block_stride, 48 * (int64_t)p->modulation))
+        return fail(WCE_EINVAL, "wce_soft_demap: llr strides too small");
+    if (reinterpret_cast<uintptr_t>(eq) % 16 || reinterpret_cast<uintptr_t>(p->h) % 16 ||
+        reinterpret_cast<uintptr_t>(p->h_lt) % 16)
+        return fail(WCE_EINVAL, "wce_soft_demap: eq, h or h_lt not 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(llr) % 4) return fail(WCE_EINVAL, "wce_soft_demap: llr not 4-byte aligned");
+    if (n == 0) return WCE_OK;
+    wce::DemapArgs a{};
+    a.eq = reinterpret_cast<const double *>(eq);
+    a.h = reinterpret_cast<const double *>(p->h);
+    a.hlt = reinterpret_cast<const double *>(p->h_lt);
+    a.efs = eq_frame_stride; a.ebs = eq_block_stride; a.hs = p->h_stride; a.n = n;
+    a.mod = p->modulation; a.d = p->scale * K;
+    a.llr = llr; a.lfs = llr_frame_stride; a.lbs = llr_block_stride;
+    DeviceGuard g(c->device);
+    const int rc = wce::launch_demap(a, stream);
+    return rc ? fail(rc, "soft demap launch") : WCE_OK;
+}
+
+int wce_viterbi_decode(wce_ctx *c, const float *llr, int64_t llr_frame_stride, int64_t llr_block_stride,
+                       int32_t modulation, int32_t rate, uint32_t flags, int64_t n, uint8_t *bits,
+                       int64_t bits_stride, const uint8_t *ref_bits, int64_t ref_stride, uint32_t *nbiterr,
+                       void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    if (!llr) return fail(WCE_EINVAL, "wce_viterbi_decode: null llr");
+    const int T = wce::decode_info_bits(modulation, rate);
+    if (T < 0) return fail(WCE_EINVAL, "wce_viterbi_decode: unknown modulation or rate");
+    if (flags & ~WCE_DEC_TERMINATED) return fail(WCE_EINVAL, "wce_viterbi_decode: unknown flag bits");
+    if (!bits && !nbiterr) return fail(WCE_EINVAL, "wce_viterbi_decode: no output requested");
+    if (nbiterr && !ref_bits) return fail(WCE_EINVAL, "wce_viterbi_decode: nbiterr needs ref_bits");
+    if (n < 0 || n > 0x7fffffffll) return fail(WCE_EINVAL, "wce_viterbi_decode: n_frames < 0 or > 2^31 - 1");
+    if (!strides_hold(n, llr_frame_stride, llr_block_stride, 48 * (int64_t)modulation))
+        return fail(WCE_EINVAL, "wce_viterbi_decode: llr strides too small");
+    const int64_t nbytes = (T + 7) / 8;
+    if (bits && bits_stride < nbytes) return fail(WCE_EINVAL, "wce_viterbi_decode: bits_stride < ceil(T / 8)");
+    if (ref_bits && ref_stride < nbytes) return fail(WCE_EINVAL, "wce_viterbi_decode: ref_stride < ceil(T / 8)");
+    if (reinterpret_cast<uintptr_t>(llr) % 4 || reinterpret_cast<uintptr_t>(nbiterr) % 4)
+        return fail(WCE_EINVAL, "wce_viterbi_decode: llr or nbiterr not 4-byte aligned");
+    if (n == 0) return WCE_OK;
+    wce::ViterbiArgs a{};
+    a.llr = llr; a.lfs = llr_frame_stride; a.lbs = llr_block_stride; a.n = n;
+    a.mod = modulation; a.rate = rate; a.T = T; a.flags = flags;
+    a.bits = bits; a.bits_stride = bits_stride;
+    a.ref = ref_bits; a.ref_stride = ref_stride;
+    a.nbiterr = nbiterr;
+    DeviceGuard g(c->device);
+    const int rc = wce::launch_viterbi(a, stream);
+    if (rc == WCE_EINVAL) return fail(rc, "wce_viterbi_decode: the survivor memory of T steps does not fit the LDS");
+    return rc ? fail(rc, "viterbi launch") : WCE_OK;
+}
+
 // ---------------------------------------------------------------- runtime helpers
 int wce_device_count(int *count)
 {

@@ -238,8 +238,36 @@ struct DemodArgs {
     int64_t eqfs, eqbs, symfs, symbs;
 };
 
+// soft demapper (wce_decode.hip): eq[f*efs + b*ebs + k], h / hlt rows of stride hs (hlt null: no blend),
+// llr[f*lfs + b*lbs + (0..48 mod - 1)] in deinterleaved coded order
+struct DemapArgs {
+    const double *eq, *h, *hlt;
+    int64_t efs, ebs, hs, n;
+    int32_t mod;          // WCE_MOD_*: bits per data symbol
+    double d;             // level half-spacing scale K
+    float *llr;
+    int64_t lfs, lbs;
+};
+
+// Viterbi decoder (wce_decode.hip): T = decode_info_bits(mod, rate) trellis steps per frame
+struct ViterbiArgs {
+    const float *llr;
+    int64_t lfs, lbs, n;
+    int32_t mod, rate, T;
+    uint32_t flags;       // WCE_DEC_*
+    uint8_t *bits;        // may be null
+    const uint8_t *ref;   // may be null
+    uint32_t *nbiterr;    // may be null
+    int64_t bits_stride, ref_stride;
+};
+
 int launch_ls(const State *st, const LsArgs &a, void *stream);
 int launch_demod(const DemodArgs &a, void *stream);
+int launch_demap(const DemapArgs &a, void *stream);
+// WCE_EINVAL where the survivor memory of T steps does not fit a workgroup's LDS
+int launch_viterbi(const ViterbiArgs &a, void *stream);
+// information bits per frame, or WCE_EINVAL for an unknown modulation or rate
+int decode_info_bits(int mod, int rate);
 // a.start != null: the per-frame-start builds; else a.cfo != null: the CFO builds
 int launch_front(const FrontArgs &a, bool preamble, void *stream);
 // cus: the device's CU count, which caps the grid

@@ -45,6 +45,8 @@ SEM_MATLAB = 1     # WiFi_channel_estimation_*.m semantics
 MOD_BPSK, MOD_QPSK, MOD_QAM16, MOD_QAM64 = 1, 2, 4, 6   # wce_demod.modulation: bits per data symbol
 DEMOD_TRACK = 1 << 0     # remove each block's common pilot phase
 DEMOD_REF_TX = 1 << 1    # EVM against tx instead of the decided point
+RATE_1_2, RATE_2_3, RATE_3_4 = 0, 1, 2   # WCE_RATE_*: code rate of wce_viterbi_decode
+DEC_TERMINATED = 1 << 0  # WCE_DEC_TERMINATED: trace back from state 0
 
 STATUS = {0: "ok", -1: "invalid argument", -2: "HIP error", -3: "out of memory",
           -4: "context state not ready", -5: "no gfx950 device"}
@@ -155,6 +157,11 @@ ABI = {
     "wce_front_end_blocks_at": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64,
                                 c_void_p, c_int64, c_int64, c_void_p],
     "wce_demodulate": [c_void_p, POINTER(Frames), POINTER(Demod), POINTER(DemodOut), c_void_p],
+    "wce_soft_demap": [c_void_p, c_void_p, c_int64, c_int64, POINTER(Demod), c_int64, c_void_p, c_int64, c_int64,
+                       c_void_p],
+    "wce_viterbi_decode": [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_uint32, c_int64, c_void_p,
+                           c_int64, c_void_p, c_int64, c_void_p, c_void_p],
+    "wce_decode_info_bits": [c_int32, c_int32],
     "wce_nonfinite_scan": [c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int64, c_uint32, c_void_p, c_void_p,
                            c_void_p],
     "wce_comm_unique_id": [c_void_p],
@@ -226,6 +233,14 @@ def load(path: str = LIB_PATH):
 def _check(rc, where):
     if rc != 0:
         raise WceError(rc, where)
+
+
+def info_bits(modulation, rate) -> int:
+    """wce_decode_info_bits: information bits (trellis steps) per frame of 15 blocks, 48 data subcarriers each."""
+    T = load().wce_decode_info_bits(int(modulation), int(rate))
+    if T < 0:
+        raise WceError(T, "wce_decode_info_bits")
+    return T
 
 
 def device_count() -> int:
@@ -504,6 +519,81 @@ class Context:
         synchronize()
         return {n: a.numpy() for n, a in d.items()}
 
+    def soft_demap(self, eq, h, n_frames, h_lt=None, h_stride=NSC, modulation=MOD_BPSK, scale=8.8753, llr=None,
+                   eq_frame_stride=None, eq_block_stride=NSC, llr_frame_stride=None, llr_block_stride=None,
+                   stream=None):
+        """wce_soft_demap on device arrays: the equalized symbols eq complex [n][15][eq_block_stride] (e.g.
+        demodulate's) and the estimate h [n][h_stride] (blended with h_lt over the blocks, if given, as
+        demodulate blends) -> llr float32 [n][15][llr_block_stride]: per block the 48 * modulation max-log soft
+        bits |Hu|^2 (D0 - D1) in deinterleaved coded order, > 0 for bit 1, 0 where eq or Hu is not finite.
+        Block strides default to 53 and 48 * modulation, frame strides to 15 block strides."""
+        lbs = llr_block_stride if llr_block_stride is not None else 48 * modulation
+        p = Demod(_addr(h), _addr(h_lt), h_stride, modulation, 0, scale)
+        _check(_lib.wce_soft_demap(self.handle, _addr(eq),
+                                   eq_frame_stride if eq_frame_stride is not None else NBLK * eq_block_stride,
+                                   eq_block_stride, byref(p), n_frames, _addr(llr),
+                                   llr_frame_stride if llr_frame_stride is not None else NBLK * lbs, lbs, stream),
+               "wce_soft_demap")
+
+    def viterbi_decode(self, llr, n_frames, modulation, rate, terminated=True, bits=None, bits_stride=None,
+                       ref_bits=None, ref_stride=None, nbiterr=None, llr_frame_stride=None, llr_block_stride=None,
+                       stream=None):
+        """wce_viterbi_decode on device arrays: llr float32 [n][15][llr_block_stride] (soft_demap's) of
+        `modulation` at code rate `rate` (RATE_*) -> bits uint8 [n][bits_stride], the info_bits(modulation, rate)
+        information bits packed LSB first, and/or nbiterr uint32 [n], the bits that differ from ref_bits (packed
+        the same way, [n][ref_stride]).  terminated: the traceback starts from state 0.  The byte strides default
+        to ceil(T / 8), the block stride to 48 * modulation, the frame stride to 15 block strides."""
+        lbs = llr_block_stride if llr_block_stride is not None else 48 * modulation
+        nbytes = (info_bits(modulation, rate) + 7) // 8
+        _check(_lib.wce_viterbi_decode(self.handle, _addr(llr),
+                                       llr_frame_stride if llr_frame_stride is not None else NBLK * lbs, lbs,
+                                       modulation, rate, DEC_TERMINATED if terminated else 0, n_frames, _addr(bits),
+                                       bits_stride if bits_stride is not None else nbytes, _addr(ref_bits),
+                                       ref_stride if ref_stride is not None else nbytes, _addr(nbiterr), stream),
+               "wce_viterbi_decode")
+
+    def _decode_device(self, deq, dh, dhlt, B, modulation, rate, scale, terminated, ref_bits):
+        """queue soft_demap and viterbi_decode on dense device arrays (eq [B][15][53], h and h_lt [B][53]);
+        -> name -> DeviceArray (read them after a synchronize, through _decode_result)"""
+        T = info_bits(modulation, rate)
+        d = {"llr": DeviceArray((B, NBLK, 48 * modulation), np.float32, zero=True),
+             "bits": DeviceArray((B, (T + 7) // 8), np.uint8, zero=True)}
+        dref = None
+        if ref_bits is not None:
+            ref = np.asarray(ref_bits, np.uint8)
+            if ref.shape != (B, T):
+                raise ValueError("ref_bits must be [B][T] with T = info_bits(modulation, rate)")
+            dref = DeviceArray.from_numpy(np.packbits(ref, axis=1, bitorder="little"))
+            d["nbiterr"] = DeviceArray((B,), np.uint32, zero=True)
+        self.soft_demap(deq, dh, B, dhlt, NSC, modulation, scale, d["llr"])
+        self.viterbi_decode(d["llr"], B, modulation, rate, terminated, d["bits"], ref_bits=dref,
+                            nbiterr=d.get("nbiterr"))
+        d["_ref"] = dref   # read by the queued decoder until the caller synchronises
+        return d
+
+    @staticmethod
+    def _decode_result(d, modulation, rate):
+        res = {n: a.numpy() for n, a in d.items() if n != "_ref"}
+        res["bits"] = np.unpackbits(res["bits"], axis=1, bitorder="little")[:, :info_bits(modulation, rate)]
+        return res
+
+    def decode_host(self, eq, h, h_lt=None, modulation=MOD_BPSK, rate=RATE_1_2, scale=8.8753, terminated=True,
+                    ref_bits=None):
+        """Convenience: host equalized symbols eq [B][15][53] (demodulate_host's) and estimates h (and h_lt)
+        [B][53] -> dict of host arrays: llr float32 [B][15][48 * modulation] (soft_demap), bits uint8 [B][T],
+        one information bit per entry (viterbi_decode, unpacked), and, with ref_bits [B][T], nbiterr uint32 [B]."""
+        eq, h = _as_c128(eq), _as_c128(h)
+        B = eq.shape[0]
+        if eq.shape != (B, NBLK, NSC):
+            raise ValueError("eq must be [B][15][53] complex")
+        if h.shape != (B, NSC) or (h_lt is not None and np.shape(h_lt) != (B, NSC)):
+            raise ValueError("h / h_lt must be [B][53] complex")
+        deq, dh = DeviceArray.from_numpy(eq), DeviceArray.from_numpy(h)
+        dhlt = DeviceArray.from_numpy(_as_c128(h_lt)) if h_lt is not None else None
+        d = self._decode_device(deq, dh, dhlt, B, modulation, rate, scale, terminated, ref_bits)
+        synchronize()
+        return self._decode_result(d, modulation, rate)
+
     def mmse_solve(self, frames: Frames, W, w_stride=NSC, stream=None):
         _check(_lib.wce_mmse_solve(self.handle, byref(frames), _addr(W), w_stride, stream), "wce_mmse_solve")
 
@@ -623,10 +713,13 @@ class Context:
         dtp = DeviceArray.from_numpy(_as_c128(tx_pre)) if tx_pre is not None else None
         return self._estimate_device(dtx, drx, dpre, B, mask, block, eq_source, semantics, dtp, ls_f32, dow2)
 
-    def _estimate_device(self, dtx, drx, dpre, B, mask, block, eq_source, semantics, dtp, ls_f32, dow2, demod=None):
+    def _estimate_device(self, dtx, drx, dpre, B, mask, block, eq_source, semantics, dtp, ls_f32, dow2, demod=None,
+                         decode=None):
         """estimate_host's device half: dense [B][15][53] frames (and rx_pre [B][53], tx_pre [53], ow2 [B] or
         None) on the device -> dict of host outputs.  demod: (source bit, modulation, scale, track) queues
-        demodulate behind the estimate with h = that estimator's output and h_lt = lt_ls; the dict gains "demod"."""
+        demodulate behind the estimate with h = that estimator's output and h_lt = lt_ls; the dict gains "demod".
+        decode (needs demod): (rate, ref_bits, terminated) queues soft_demap and viterbi_decode behind that, on
+        the demodulated eq where it lies on the device; the dict gains "decode"."""
         names = [("lt_ls", LT_LS), ("ps_linear", PS_LINEAR), ("ps_cubic", PS_CUBIC), ("ps_sinc", PS_SINC),
                  ("ps_mmse", PS_MMSE)]
         lsdt = np.complex64 if ls_f32 else np.complex128
@@ -638,16 +731,21 @@ class Context:
                     OUT_LS_F32 if ls_f32 else 0)
         fr = self.frames(dtx, drx, B, rx_pre=dpre, block=block, semantics=semantics, tx_pre=dtp)
         self.estimate(fr, o, mask, ow2=dow2)
-        dem = None
+        dem = dec = None
         if demod is not None:   # same (null) stream: it reads the estimate's outputs in order, no host hop
             src = {bit: n for n, bit in names}[demod[0]]
             dem = self._demod_device(fr, B, outs[src], outs["lt_ls"], demod[1], demod[2], demod[3], True)
+            if decode is not None:
+                dec = self._decode_device(dem["eq"], outs[src], outs["lt_ls"], B, demod[1], decode[0], demod[2],
+                                          decode[2], decode[1])
         synchronize()
         res = {n: outs[n].numpy() for n in outs}
         if deq is not None:
             res["eq"] = deq.numpy()
         if dem is not None:
             res["demod"] = {n: a.numpy() for n, a in dem.items()}
+        if dec is not None:
+            res["decode"] = self._decode_result(dec, demod[1], decode[0])
         return res
 
     @staticmethod
@@ -661,8 +759,19 @@ class Context:
             raise ValueError("demod_source and LT_LS must be in mask")
         return (demod_source, modulation, scale, track)
 
+    @staticmethod
+    def _decode_request(decode_rate, dem, ref_bits, terminated):
+        """receive_host's decode_rate: None, or a RATE_* value beside a demod_source"""
+        if decode_rate is None:
+            return None
+        if dem is None:
+            raise ValueError("decode_rate needs demod_source")
+        info_bits(dem[1], decode_rate)   # raises for an unknown modulation or rate
+        return (decode_rate, ref_bits, terminated)
+
     def receive_host(self, tx_packets, tx_lptot, rx_packets, rx_lptot, mask=ALL, semantics=SEM_MATLAB, cfo=False,
-                     sample_offset=0, demod_source=None, modulation=MOD_BPSK, scale=8.8753, track=True):
+                     sample_offset=0, demod_source=None, modulation=MOD_BPSK, scale=8.8753, track=True,
+                     decode_rate=None, ref_bits=None, terminated=True):
         """WiFi_RX.m:17-60 for a batch, on the device with no host hop in between: host time-domain packets
         [B][>= 1200] and long training fields [B][L] of both sides -> the front end (symbols, preamble FFTs and
         each packet's sigma^2) -> estimate with each frame's own rx preamble (WCE_MMSE_FRAME_COV) and own
@@ -676,8 +785,13 @@ class Context:
         demod_source: an estimator bit of `mask` (PS_MMSE included; LT_LS must be in mask too): the frames are
         demodulated with h = that estimator's output and h_lt = the frame's lt_ls (demodulate: `modulation`,
         `scale`, `track`, EVM against tx), queued behind the estimate; the dict gains "demod", the dict of
-        demodulate_host.  None: no demodulation."""
+        demodulate_host.  None: no demodulation.
+        decode_rate: a RATE_* value (demod_source must be set): the demodulated eq stays on the device and is
+        demapped and decoded there (soft_demap with the same h and h_lt, viterbi_decode at that rate, `terminated`),
+        queued behind the demodulation; the dict gains "decode", the dict of decode_host (nbiterr with ref_bits
+        [B][T]).  A frame of NaN symbols decodes from all-zero soft bits to all-zero bits."""
         dem = self._demod_request(demod_source, mask, modulation, scale, track)
+        dcd = self._decode_request(decode_rate, dem, ref_bits, terminated)
         pk = [_as_c128(tx_packets), _as_c128(rx_packets)]
         lp = [_as_c128(tx_lptot), _as_c128(rx_lptot)]
         B = pk[1].shape[0]
@@ -703,7 +817,7 @@ class Context:
             pre.append(dpre)
         # same (null) stream throughout: the estimate reads the front end's outputs in order
         res = self._estimate_device(sym[0], sym[1], pre[1], B, mask | FRAME_COV, 0, PS_LINEAR, semantics, pre[0],
-                                    False, dow2, dem)
+                                    False, dow2, dem, dcd)
         res["ow2"] = dow2.numpy()
         if cfo:
             res["cfo"] = dcfo.numpy()
@@ -711,7 +825,8 @@ class Context:
 
     def receive_capture_host(self, tx_packets, tx_lptot, rx_capture, threshold, backoff=0, mask=ALL,
                              semantics=SEM_MATLAB, cfo=False, sample_offset=0, demod_source=None,
-                             modulation=MOD_BPSK, scale=8.8753, track=True):
+                             modulation=MOD_BPSK, scale=8.8753, track=True, decode_rate=None, ref_bits=None,
+                             terminated=True):
         """receive_host with the rx side taken from raw capture windows [B][capture_len], in which each packet
         (long training field, then sample_offset samples, then the packet) starts at an unknown sample:
         front_end_sync against tx_lptot[0][-64:] finds each window's start (start - backoff, or -1 where the
@@ -719,8 +834,10 @@ class Context:
         all queued on one stream with no host hop.  The dict gains "start" [B] int32 and "metric" [B]; a
         window without a detected packet, or one the packet does not fit in, gives NaN rows.
         demod_source, modulation, scale, track: as receive_host; such a window's "demod" has NaN evm and
-        0xFF symbols."""
+        0xFF symbols.  decode_rate, ref_bits, terminated: as receive_host; such a window's "decode" has
+        all-zero soft bits and all-zero bits."""
         dem = self._demod_request(demod_source, mask, modulation, scale, track)
+        dcd = self._decode_request(decode_rate, dem, ref_bits, terminated)
         pk, lp, cap = _as_c128(tx_packets), _as_c128(tx_lptot), _as_c128(rx_capture)
         if cap.ndim != 2 or cap.shape[1] < 2 * FFT_SIZE:
             raise ValueError("rx_capture must be [B][>= 128] complex")
@@ -744,7 +861,7 @@ class Context:
         self.front_end_blocks(dcap, B, NBLK, sym[1], cfo=dcfo, sample_offset=sample_offset, start=dstart,
                               capture_len=W)
         res = self._estimate_device(sym[0], sym[1], pre[1], B, mask | FRAME_COV, 0, PS_LINEAR, semantics, pre[0],
-                                    False, dow2, dem)
+                                    False, dow2, dem, dcd)
         res["ow2"] = dow2.numpy()
         if cfo:
             res["cfo"] = dcfo.numpy()

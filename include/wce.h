@@ -481,6 +481,80 @@ typedef struct {              /* every pointer device, each may be NULL = not wa
 
 int wce_demodulate(wce_ctx *ctx, const wce_frames *in, const wce_demod *p, const wce_demod_out *out, void *stream);
 
+/* ---- decoding: soft demapper, deinterleaver, Viterbi decoder (IEEE 802.11-2020
+ * 17.3.5.5 to 17.3.5.8; the reference stops at the equalized symbols) ----
+ * Every 802.11a/g/p payload is convolutionally coded, punctured and interleaved;
+ * these two calls take wce_demodulate's eq to information bits on the device.
+ * A frame is the 15 blocks of 48 data subcarriers every other call uses
+ * (k = 0..52 ascending without the pilots 5, 19, 33, 47 and DC 26).  With bpsc =
+ * the WCE_MOD_* value (1, 2, 4, 6) and R the WCE_RATE_* fraction:
+ *     N_CBPS = 48 bpsc  coded bits per block,   N_TX = 15 N_CBPS  per frame,
+ *     T = N_TX R  information bits per frame = trellis steps (360 .. 3240).
+ *
+ *   code         shift register with input u_t, K = 7:
+ *                A_t = u_t ^ u_{t-2} ^ u_{t-3} ^ u_{t-5} ^ u_{t-6}   (133 octal)
+ *                B_t = u_t ^ u_{t-1} ^ u_{t-2} ^ u_{t-3} ^ u_{t-6}   (171 octal)
+ *                mother stream A_0 B_0 A_1 B_1 ...  State s, 6 bits: bit 5 = u_{t-1}, bit 0 =
+ *                u_{t-6}; the successor of s on input u is (u << 5) | (s >> 1); the encoder starts
+ *                in state 0.
+ *   puncturing   (17.3.5.6) rate 2/3 keeps the mother positions marked 1 of 1 1 1 0 (A0 B0 A1,
+ *                not B1), rate 3/4 those of 1 1 1 0 0 1 (A0 B0 A1 B2), repeating.  Depuncturing
+ *                puts LLR 0 at the dropped positions.
+ *   interleaver  (17.3.5.7) per block, s = max(bpsc / 2, 1): coded bit k goes to
+ *                i = (N_CBPS / 16)(k mod 16) + floor(k / 16), then to
+ *                j = s floor(i / s) + (i + N_CBPS - floor(16 i / N_CBPS)) mod s.
+ *                Transmitted bit j belongs to data subcarrier floor(j / bpsc), counted over the 48
+ *                data subcarriers in ascending k, and is its bit j mod bpsc, b0 first.  b0 is the
+ *                top bit of wce_demodulate's label: the first bpsc / 2 bits set the I level, the
+ *                rest the Q level, by the same Gray tables.
+ *   soft bit     (wce_soft_demap; max-log, weighted by the channel, no noise variance in it)
+ *                from e = eq[f][b][k] and Hu_b[k] = h, or the h / h_lt blend exactly as
+ *                wce_demodulate defines it:  L = |Hu_b[k]|^2 (D0 - D1),  D_c = the minimum, over
+ *                the axis levels (2 i - (M-1)) d whose Gray label has the bit equal to c, of
+ *                (v - level)^2;  v = Re e for an I bit, Im e for a Q bit;  d = scale K as in
+ *                wce_demodulate.  L > 0 favours bit 1.  A per-frame factor 1 / sigma^2 changes no
+ *                decision and is left out; scale by 1 / ow2[f] for true LLRs.  If e or Hu is not
+ *                finite every bit of that symbol gets L = 0, an erasure (the NaN row of an
+ *                undetected packet decodes from all-zero LLRs).  fp64 arithmetic, rounded once to
+ *                float.  Output in DEINTERLEAVED coded order:
+ *                llr[f*llr_frame_stride + b*llr_block_stride + k], k < N_CBPS.
+ *   decoder      (wce_viterbi_decode) maximum-correlation Viterbi over the depunctured stream,
+ *                float metrics, pm_0[0] = 0, pm_0[s != 0] = -inf.  Per step, with the pair
+ *                (L_A, L_B) (a non-finite LLR reads as 0), the branch metric of predecessor p into
+ *                s' is (+-L_A) + (+-L_B), + where the branch's coded bit is 1; the predecessors of
+ *                s' are p0 = 2 (s' & 31) and p1 = p0 + 1; pm[s'] = max(pm[p0] + bm0, pm[p1] + bm1),
+ *                p0 wins a tie.  No renormalisation (3240 steps of float need none).  With
+ *                WCE_DEC_TERMINATED the traceback starts from state 0 (the caller's last six
+ *                information bits are 0), else from the state of the largest final metric, the
+ *                lowest state of a tie.  Decoded bit t is bit 5 of the survivor's state after step t.
+ *
+ *  - bits[f*bits_stride + (t >> 3)], bit t & 7, is information bit t (packed, LSB first); the
+ *    unused high bits of the last byte are written 0.  ref_bits is packed the same way and
+ *    nbiterr[f] is the number of the T decoded bits that differ from it.
+ *  - Both calls are asynchronous on `stream`, read nothing back, allocate nothing and need
+ *    only a device-selecting ctx: demodulate, demap and decode queue on one stream with no
+ *    host hop.  A frame's results depend only on its own data and the call's arguments.
+ *    wce_soft_demap reads p->h, h_lt, h_stride, modulation and scale; p->flags is ignored.
+ *  - WCE_EINVAL (text in wce_last_error()) before any launch: a NULL ctx, eq, p, p->h or llr;
+ *    an unknown modulation or rate, or an unknown flag bit; scale not positive and finite;
+ *    h_stride < 53; a block stride < N_CBPS (< 53 for eq) or, with more than one frame, a frame
+ *    stride < 14 block strides + one row (N_CBPS, 53 for eq); bits_stride < ceil(T / 8) (with
+ *    bits), ref_stride likewise (with ref_bits); nbiterr without ref_bits; neither bits nor
+ *    nbiterr; eq, h or h_lt not 16-byte aligned; llr or nbiterr not 4-byte aligned; n_frames < 0
+ *    or > 2^31 - 1.  n_frames == 0 is WCE_OK.
+ *  - wce_decode_info_bits: T for a modulation and rate, or WCE_EINVAL. */
+enum { WCE_RATE_1_2 = 0, WCE_RATE_2_3 = 1, WCE_RATE_3_4 = 2 };
+#define WCE_DEC_TERMINATED (1u << 0)   /* trace back from state 0 */
+
+int wce_soft_demap(wce_ctx *ctx, const wce_complex *eq, int64_t eq_frame_stride, int64_t eq_block_stride,
+                   const wce_demod *p, int64_t n_frames, float *llr, int64_t llr_frame_stride,
+                   int64_t llr_block_stride, void *stream);
+int wce_viterbi_decode(wce_ctx *ctx, const float *llr, int64_t llr_frame_stride, int64_t llr_block_stride,
+                       int32_t modulation, int32_t rate, uint32_t flags, int64_t n_frames, uint8_t *bits,
+                       int64_t bits_stride, const uint8_t *ref_bits, int64_t ref_stride, uint32_t *nbiterr,
+                       void *stream);
+int wce_decode_info_bits(int32_t modulation, int32_t rate);
+
 /* Non-finite guard.  The reference passes NaN/Inf through
  * silently: main.c's PS_MMSE returns NaN x 53 (main.c:148-212), a zero pilot
  * makes PS_* divide by zero (main.c:82-84), and its dimension checks only
