@@ -1151,6 +1151,53 @@ int wce_viterbi_decode(wce_ctx *c, const float *llr, int64_t llr_frame_stride, i
     return rc ? fail(rc, "viterbi launch") : WCE_OK;
 }
 
+// ---------------------------------------------------------------- decision-directed estimation
+int wce_reencode(wce_ctx *c, const wce_reencode_par *p, const wce_frames *in, int64_t n,
+                 const wce_reencode_out *out, void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    if (!p || !out) return fail(WCE_EINVAL, "wce_reencode: null parameters or outputs");
+    if (!p->bits) return fail(WCE_EINVAL, "wce_reencode: bits required");
+    if (!out->tx && !out->h) return fail(WCE_EINVAL, "wce_reencode: no output requested");
+    if (out->h && (!in || !in->rx)) return fail(WCE_EINVAL, "wce_reencode: h needs the frames' rx");
+    if (n < 0 || n > 0x7fffffffll) return fail(WCE_EINVAL, "wce_reencode: n_frames < 0 or > 2^31 - 1");
+    if (in && in->n_frames != n) return fail(WCE_EINVAL, "wce_reencode: the frames' n_frames differs from n_frames");
+    const int T = wce::decode_info_bits(p->modulation, p->rate);
+    if (T < 0) return fail(WCE_EINVAL, "wce_reencode: unknown modulation or rate");
+    double K;
+    switch (p->modulation) {   // the doubles nearest to 1 / sqrt(1, 2, 10, 42), as wce_demodulate
+    case WCE_MOD_BPSK: K = 1.0; break;
+    case WCE_MOD_QPSK: K = 0.70710678118654752440; break;
+    case WCE_MOD_QAM16: K = 0.31622776601683793320; break;
+    default: K = 0.15430334996209191026; break;
+    }
+    if (!(p->scale > 0.0) || p->scale * 0.0 != 0.0) return fail(WCE_EINVAL, "wce_reencode: scale not positive and finite");
+    if (p->bits_stride < (T + 7) / 8) return fail(WCE_EINVAL, "wce_reencode: bits_stride < ceil(T / 8)");
+    if (out->tx && !strides_hold(n, out->tx_frame_stride, out->tx_block_stride, wce::NSC))
+        return fail(WCE_EINVAL, "wce_reencode: tx strides too small");
+    if (in && !strides_hold(n, in->frame_stride, in->block_stride, wce::NSC))
+        return fail(WCE_EINVAL, "wce_reencode: the frames' strides too small");
+    if (out->h && out->h_stride < wce::NSC) return fail(WCE_EINVAL, "wce_reencode: h_stride < 53");
+    if (reinterpret_cast<uintptr_t>(out->tx) % 16 || reinterpret_cast<uintptr_t>(out->h) % 16 ||
+        (in && (reinterpret_cast<uintptr_t>(in->rx) % 16 || reinterpret_cast<uintptr_t>(in->tx) % 16)))
+        return fail(WCE_EINVAL, "wce_reencode: tx, h or the frames' rx or tx not 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(p->theta) % 8) return fail(WCE_EINVAL, "wce_reencode: theta not 8-byte aligned");
+    if (n == 0) return WCE_OK;
+    wce::ReencodeArgs a{};
+    a.bits = p->bits; a.bits_stride = p->bits_stride;
+    a.theta = out->h ? p->theta : nullptr;
+    a.ptx = in ? reinterpret_cast<const double *>(in->tx) : nullptr;
+    a.rx = out->h ? reinterpret_cast<const double *>(in->rx) : nullptr;
+    if (in) { a.fs = in->frame_stride; a.bs = in->block_stride; }
+    a.n = n; a.mod = p->modulation; a.rate = p->rate;
+    a.scale = p->scale; a.d = p->scale * K;
+    a.tx = reinterpret_cast<double *>(out->tx); a.tfs = out->tx_frame_stride; a.tbs = out->tx_block_stride;
+    a.h = reinterpret_cast<double *>(out->h); a.hs = out->h_stride;
+    DeviceGuard g(c->device);
+    const int rc = wce::launch_reencode(a, stream);
+    return rc ? fail(rc, "reencode launch") : WCE_OK;
+}
+
 // ---------------------------------------------------------------- runtime helpers
 int wce_device_count(int *count)
 {

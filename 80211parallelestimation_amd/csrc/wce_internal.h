@@ -261,9 +261,23 @@ struct ViterbiArgs {
     int64_t bits_stride, ref_stride;
 };
 
+// re-encoder and data-aided LS (wce_reencode.hip): packed information bits bits[f*bits_stride + ...]; frames as
+// LsArgs (rx read for h; ptx = the frames' tx, of which the pilot entries are read, null: 802.11's pilots)
+struct ReencodeArgs {
+    const uint8_t *bits;
+    const double *theta;  // theta[f*15 + b], may be null
+    const double *ptx, *rx;
+    int64_t bits_stride, fs, bs, n;
+    int32_t mod, rate;    // WCE_MOD_*, WCE_RATE_*
+    double scale, d;      // pilot and data level half-spacing: scale, scale K
+    double *tx, *h;       // each may be null, not both
+    int64_t tfs, tbs, hs;
+};
+
 int launch_ls(const State *st, const LsArgs &a, void *stream);
 int launch_demod(const DemodArgs &a, void *stream);
 int launch_demap(const DemapArgs &a, void *stream);
+int launch_reencode(const ReencodeArgs &a, void *stream);
 // WCE_EINVAL where the survivor memory of T steps does not fit a workgroup's LDS
 int launch_viterbi(const ViterbiArgs &a, void *stream);
 // information bits per frame, or WCE_EINVAL for an unknown modulation or rate

@@ -100,6 +100,18 @@ class DemodOut(ctypes.Structure):
                 ("sym_block_stride", c_int64)]
 
 
+class ReencodePar(ctypes.Structure):
+    """struct wce_reencode_par (include/wce.h)."""
+    _fields_ = [("bits", c_void_p), ("bits_stride", c_int64), ("modulation", c_int32), ("rate", c_int32),
+                ("scale", c_double), ("theta", c_void_p)]
+
+
+class ReencodeOut(ctypes.Structure):
+    """struct wce_reencode_out (include/wce.h)."""
+    _fields_ = [("tx", c_void_p), ("tx_frame_stride", c_int64), ("tx_block_stride", c_int64), ("h", c_void_p),
+                ("h_stride", c_int64)]
+
+
 _lib = None
 
 # (name, argtypes) for every symbol include/wce.h and include/wce_compat.h declare
@@ -162,6 +174,7 @@ ABI = {
     "wce_viterbi_decode": [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_uint32, c_int64, c_void_p,
                            c_int64, c_void_p, c_int64, c_void_p, c_void_p],
     "wce_decode_info_bits": [c_int32, c_int32],
+    "wce_reencode": [c_void_p, POINTER(ReencodePar), POINTER(Frames), c_int64, POINTER(ReencodeOut), c_void_p],
     "wce_nonfinite_scan": [c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int64, c_uint32, c_void_p, c_void_p,
                            c_void_p],
     "wce_comm_unique_id": [c_void_p],
@@ -552,6 +565,53 @@ class Context:
                                        ref_stride if ref_stride is not None else nbytes, _addr(nbiterr), stream),
                "wce_viterbi_decode")
 
+    def reencode(self, bits, n_frames, modulation, rate, scale=8.8753, bits_stride=None, theta=None, frames=None,
+                 tx=None, tx_frame_stride=None, tx_block_stride=NSC, h=None, h_stride=NSC, stream=None):
+        """wce_reencode on device arrays: bits uint8 [n][bits_stride] (viterbi_decode's packed information bits) of
+        `modulation` at code rate `rate` -> tx complex [n][15][tx_block_stride], the symbols the transmitter sent
+        for them (pilots copied from frames.tx where `frames` has one, else 802.11's; DC 0), and/or h complex
+        [n][h_stride], the data-aided LS estimate sum_b conj(tx_b) rx_b r_b / sum_b |tx_b|^2 against frames.rx with
+        the rotors r_b = exp(-i theta[n][b]) (theta float64 [n][15] as demodulate writes it; None: 1).  bits_stride
+        defaults to ceil(T / 8), the tx frame stride to 15 block strides."""
+        nbytes = (info_bits(modulation, rate) + 7) // 8
+        p = ReencodePar(_addr(bits), bits_stride if bits_stride is not None else nbytes, modulation, rate, scale,
+                        _addr(theta))
+        o = ReencodeOut(_addr(tx), tx_frame_stride if tx_frame_stride is not None else NBLK * tx_block_stride,
+                        tx_block_stride, _addr(h), h_stride)
+        _check(_lib.wce_reencode(self.handle, byref(p), byref(frames) if frames is not None else None, n_frames,
+                                 byref(o), stream), "wce_reencode")
+
+    def _dd_device(self, fr, B, dbits, dtheta, modulation, rate, scale, terminated, dref, rounds):
+        """queue `rounds` decision-directed passes behind a decode, on the same (null) stream with no host read:
+        reencode(bits, theta -> h_dd) -> demodulate(h = h_dd, no blend, tracked) -> soft_demap -> viterbi_decode,
+        each round on the bits and the block phases of the one before.  fr: the frames (rx, and tx for the
+        pilots); dref: packed reference bits on the device or None.  -> name -> DeviceArray of the last round
+        (h_dd, bits, nbiterr with dref; read them after a synchronize)"""
+        T = info_bits(modulation, rate)
+        d = {}
+        for _ in range(rounds):
+            d = {"h_dd": DeviceArray((B, NSC), zero=True), "bits": DeviceArray((B, (T + 7) // 8), np.uint8, zero=True),
+                 "_keep": (dbits, dtheta, d)}   # read by the queued calls until the caller synchronises
+            eq, theta = DeviceArray((B, NBLK, NSC), zero=True), DeviceArray((B, NBLK), np.float64, zero=True)
+            llr = DeviceArray((B, NBLK, 48 * modulation), np.float32, zero=True)
+            if dref is not None:
+                d["nbiterr"] = DeviceArray((B,), np.uint32, zero=True)
+            self.reencode(dbits, B, modulation, rate, scale, theta=dtheta, frames=fr, h=d["h_dd"])
+            self.demodulate(fr, d["h_dd"], None, NSC, modulation, scale, True, True, eq=eq, theta=theta)
+            self.soft_demap(eq, d["h_dd"], B, None, NSC, modulation, scale, llr)
+            self.viterbi_decode(llr, B, modulation, rate, terminated, d["bits"], ref_bits=dref,
+                                nbiterr=d.get("nbiterr"))
+            d["_keep"] += (eq, llr, theta)
+            dbits, dtheta = d["bits"], theta
+        return d
+
+    @staticmethod
+    def _dd_result(d, modulation, rate):
+        """-> (h_dd, decode_dd) of _dd_device's dict, on the host"""
+        dd = {n: d[n].numpy() for n in ("bits", "nbiterr") if n in d}
+        dd["bits"] = np.unpackbits(dd["bits"], axis=1, bitorder="little")[:, :info_bits(modulation, rate)]
+        return d["h_dd"].numpy(), dd
+
     def _decode_device(self, deq, dh, dhlt, B, modulation, rate, scale, terminated, ref_bits):
         """queue soft_demap and viterbi_decode on dense device arrays (eq [B][15][53], h and h_lt [B][53]);
         -> name -> DeviceArray (read them after a synchronize, through _decode_result)"""
@@ -578,10 +638,17 @@ class Context:
         return res
 
     def decode_host(self, eq, h, h_lt=None, modulation=MOD_BPSK, rate=RATE_1_2, scale=8.8753, terminated=True,
-                    ref_bits=None):
+                    ref_bits=None, dd_iterations=0, rx=None, tx_pilots=None):
         """Convenience: host equalized symbols eq [B][15][53] (demodulate_host's) and estimates h (and h_lt)
         [B][53] -> dict of host arrays: llr float32 [B][15][48 * modulation] (soft_demap), bits uint8 [B][T],
-        one information bit per entry (viterbi_decode, unpacked), and, with ref_bits [B][T], nbiterr uint32 [B]."""
+        one information bit per entry (viterbi_decode, unpacked), and, with ref_bits [B][T], nbiterr uint32 [B].
+        dd_iterations n > 0 (needs rx [B][15][53], the received frames): n decision-directed rounds follow on the
+        device with no host read in between -- the decoded bits are re-encoded and the channel is estimated from
+        all 48 x 15 data symbols (reencode), rx is demodulated again with that estimate (no blend, tracked),
+        demapped and decoded.  The first round removes the block phases a tracked demodulate gives for h and h_lt,
+        the later ones those of the round before.  The pilots are tx_pilots' ([B][15][53], only the entries 5, 19,
+        33 and 47 of each block are read) or 802.11's.  The dict gains "h_dd" [B][53] and "decode_dd", the last
+        round's bits (and nbiterr); what it held without the rounds is unchanged."""
         eq, h = _as_c128(eq), _as_c128(h)
         B = eq.shape[0]
         if eq.shape != (B, NBLK, NSC):
@@ -591,8 +658,28 @@ class Context:
         deq, dh = DeviceArray.from_numpy(eq), DeviceArray.from_numpy(h)
         dhlt = DeviceArray.from_numpy(_as_c128(h_lt)) if h_lt is not None else None
         d = self._decode_device(deq, dh, dhlt, B, modulation, rate, scale, terminated, ref_bits)
+        dd = None
+        if dd_iterations:
+            if rx is None or np.shape(rx) != (B, NBLK, NSC):
+                raise ValueError("dd_iterations needs rx [B][15][53] complex")
+            if tx_pilots is not None and np.shape(tx_pilots) != (B, NBLK, NSC):
+                raise ValueError("tx_pilots must be [B][15][53] complex")
+            drx = DeviceArray.from_numpy(_as_c128(rx))
+            if tx_pilots is not None:
+                dtx = DeviceArray.from_numpy(_as_c128(tx_pilots))
+            else:   # 802.11's pilots, from the re-encoder itself
+                dtx = DeviceArray((B, NBLK, NSC), zero=True)
+                self.reencode(d["bits"], B, modulation, rate, scale, tx=dtx)
+            fr = self.frames(dtx, drx, B)
+            dtheta = DeviceArray((B, NBLK), np.float64, zero=True)
+            self.demodulate(fr, dh, dhlt, NSC, modulation, scale, True, True, theta=dtheta)
+            dd = self._dd_device(fr, B, d["bits"], dtheta, modulation, rate, scale, terminated, d["_ref"],
+                                 int(dd_iterations))
         synchronize()
-        return self._decode_result(d, modulation, rate)
+        res = self._decode_result(d, modulation, rate)
+        if dd is not None:
+            res["h_dd"], res["decode_dd"] = self._dd_result(dd, modulation, rate)
+        return res
 
     def mmse_solve(self, frames: Frames, W, w_stride=NSC, stream=None):
         _check(_lib.wce_mmse_solve(self.handle, byref(frames), _addr(W), w_stride, stream), "wce_mmse_solve")
@@ -714,12 +801,14 @@ class Context:
         return self._estimate_device(dtx, drx, dpre, B, mask, block, eq_source, semantics, dtp, ls_f32, dow2)
 
     def _estimate_device(self, dtx, drx, dpre, B, mask, block, eq_source, semantics, dtp, ls_f32, dow2, demod=None,
-                         decode=None):
+                         decode=None, dd_iterations=0):
         """estimate_host's device half: dense [B][15][53] frames (and rx_pre [B][53], tx_pre [53], ow2 [B] or
         None) on the device -> dict of host outputs.  demod: (source bit, modulation, scale, track) queues
         demodulate behind the estimate with h = that estimator's output and h_lt = lt_ls; the dict gains "demod".
         decode (needs demod): (rate, ref_bits, terminated) queues soft_demap and viterbi_decode behind that, on
-        the demodulated eq where it lies on the device; the dict gains "decode"."""
+        the demodulated eq where it lies on the device; the dict gains "decode".  dd_iterations n > 0 (needs
+        decode): n decision-directed rounds (_dd_device) behind that, on the decoder's bits and the demodulator's
+        block phases; the dict gains "h_dd" and "decode_dd"."""
         names = [("lt_ls", LT_LS), ("ps_linear", PS_LINEAR), ("ps_cubic", PS_CUBIC), ("ps_sinc", PS_SINC),
                  ("ps_mmse", PS_MMSE)]
         lsdt = np.complex64 if ls_f32 else np.complex128
@@ -731,13 +820,16 @@ class Context:
                     OUT_LS_F32 if ls_f32 else 0)
         fr = self.frames(dtx, drx, B, rx_pre=dpre, block=block, semantics=semantics, tx_pre=dtp)
         self.estimate(fr, o, mask, ow2=dow2)
-        dem = dec = None
+        dem = dec = dd = None
         if demod is not None:   # same (null) stream: it reads the estimate's outputs in order, no host hop
             src = {bit: n for n, bit in names}[demod[0]]
             dem = self._demod_device(fr, B, outs[src], outs["lt_ls"], demod[1], demod[2], demod[3], True)
             if decode is not None:
                 dec = self._decode_device(dem["eq"], outs[src], outs["lt_ls"], B, demod[1], decode[0], demod[2],
                                           decode[2], decode[1])
+                if dd_iterations:
+                    dd = self._dd_device(fr, B, dec["bits"], dem["theta"], demod[1], decode[0], demod[2], decode[2],
+                                         dec["_ref"], int(dd_iterations))
         synchronize()
         res = {n: outs[n].numpy() for n in outs}
         if deq is not None:
@@ -746,6 +838,8 @@ class Context:
             res["demod"] = {n: a.numpy() for n, a in dem.items()}
         if dec is not None:
             res["decode"] = self._decode_result(dec, demod[1], decode[0])
+        if dd is not None:
+            res["h_dd"], res["decode_dd"] = self._dd_result(dd, demod[1], decode[0])
         return res
 
     @staticmethod
@@ -790,6 +884,34 @@ class Context:
         demapped and decoded there (soft_demap with the same h and h_lt, viterbi_decode at that rate, `terminated`),
         queued behind the demodulation; the dict gains "decode", the dict of decode_host (nbiterr with ref_bits
         [B][T]).  A frame of NaN symbols decodes from all-zero soft bits to all-zero bits."""
+        return self._receive_host(tx_packets, tx_lptot, rx_packets, rx_lptot, mask, semantics, cfo, sample_offset,
+                                  demod_source, modulation, scale, track, decode_rate, ref_bits, terminated, 0)
+
+    def receive_iterated_host(self, tx_packets, tx_lptot, rx_packets, rx_lptot, demod_source, decode_rate,
+                              dd_iterations=1, **receive):
+        """receive_host(tx_packets, tx_lptot, rx_packets, rx_lptot, demod_source=..., decode_rate=..., **receive)
+        with dd_iterations decision-directed rounds queued behind its decoder, on the same stream with no host
+        read in between: the decoded bits are re-encoded and the channel is estimated from all 48 x 15 data
+        symbols, with the block phases the demodulator tracked removed (reencode; the pilots are the tx side's),
+        the frames are demodulated again with that estimate (no blend, tracked), demapped and decoded, each round
+        on the bits and phases of the one before.  -> receive_host's dict, unchanged, plus "h_dd" [B][53] and
+        "decode_dd", the last round's bits (and nbiterr with ref_bits).  dd_iterations 0: receive_host's dict."""
+        names = ("mask", "semantics", "cfo", "sample_offset", "modulation", "scale", "track", "ref_bits", "terminated")
+        unknown = set(receive) - set(names)
+        if unknown:
+            raise TypeError(f"receive_iterated_host: unknown keywords {sorted(unknown)}")
+        if dd_iterations < 0 or decode_rate is None:
+            raise ValueError("receive_iterated_host needs a decode_rate and dd_iterations >= 0")
+        kw = dict(mask=ALL, semantics=SEM_MATLAB, cfo=False, sample_offset=0, modulation=MOD_BPSK, scale=8.8753,
+                  track=True, ref_bits=None, terminated=True)
+        kw.update(receive)
+        return self._receive_host(tx_packets, tx_lptot, rx_packets, rx_lptot, kw["mask"], kw["semantics"], kw["cfo"],
+                                  kw["sample_offset"], demod_source, kw["modulation"], kw["scale"], kw["track"],
+                                  decode_rate, kw["ref_bits"], kw["terminated"], int(dd_iterations))
+
+    def _receive_host(self, tx_packets, tx_lptot, rx_packets, rx_lptot, mask, semantics, cfo, sample_offset,
+                      demod_source, modulation, scale, track, decode_rate, ref_bits, terminated, dd_iterations):
+        """receive_host's body; dd_iterations: the decision-directed rounds of receive_iterated_host"""
         dem = self._demod_request(demod_source, mask, modulation, scale, track)
         dcd = self._decode_request(decode_rate, dem, ref_bits, terminated)
         pk = [_as_c128(tx_packets), _as_c128(rx_packets)]
@@ -817,7 +939,7 @@ class Context:
             pre.append(dpre)
         # same (null) stream throughout: the estimate reads the front end's outputs in order
         res = self._estimate_device(sym[0], sym[1], pre[1], B, mask | FRAME_COV, 0, PS_LINEAR, semantics, pre[0],
-                                    False, dow2, dem, dcd)
+                                    False, dow2, dem, dcd, dd_iterations)
         res["ow2"] = dow2.numpy()
         if cfo:
             res["cfo"] = dcfo.numpy()

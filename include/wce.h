@@ -555,6 +555,67 @@ int wce_viterbi_decode(wce_ctx *ctx, const float *llr, int64_t llr_frame_stride,
                        void *stream);
 int wce_decode_info_bits(int32_t modulation, int32_t rate);
 
+/* ---- decision-directed estimation: re-encoder and data-aided LS (the reference
+ * estimates from the preamble and the 4 pilots of a block only) ----
+ * Once a frame is decoded its 48 x 15 data symbols are known again, with far fewer
+ * errors than the slicer made.  wce_reencode runs wce_viterbi_decode's information
+ * bits forwards through the code, puncturing, interleaver and bit-to-subcarrier
+ * mapping defined above to the transmitted symbols x^ (out->tx), and estimates the
+ * channel from all of them (out->h).  It is the transmitter of this library too.
+ *
+ *   x^, frame f, block b = 0..14, subcarrier k:
+ *     encoder    starts in state 0 and runs continuously over the frame's T bits,
+ *                bits[f*bits_stride + (t >> 3)], bit t & 7; the unused high bits of a row's
+ *                last byte are ignored.
+ *     punctured  the kept mother bits in order; coded bit k of block b is punctured-stream bit
+ *                b N_CBPS + k.  It is transmitted as bit j(k); data subcarrier floor(j / bpsc)
+ *                gets bit j mod bpsc, b0 first.
+ *     data       an axis whose Gray label is g has the level index i with i ^ (i >> 1) = g and
+ *                the coordinate fl((2 i - (M - 1)) d), d = fl(scale K): exactly the slicer's
+ *                decided coordinate in wce_demodulate, so a re-encoded symbol is bit-identical
+ *                to the point the slicer decides for that label.  BPSK: Im = 0.
+ *     DC         x^ = 0.
+ *     pilots     (5, 19, 33, 47) in != NULL and in->tx != NULL: copied from in->tx, the only
+ *                entries of in->tx the call reads.  Else 802.11's, scale {1, 1, 1, -1} p_b with
+ *                p_0..14 = 1 1 1 1 -1 -1 -1 1 -1 -1 -1 -1 1 1 -1 (17.3.5.10's first 15 terms).
+ *   H_dd (out->h; needs in and in->rx), the LS estimate of the channel after the block phases
+ *   the demodulator tracked are removed:
+ *       H_dd[k] = sum_b conj(x^_b[k]) rx_b[k] r_b / sum_b |x^_b[k]|^2,   H_dd[26] = 0,
+ *   b ascending; r_b = cos theta_b - i sin theta_b with p->theta, 1 without it (and where
+ *   r_b = 1 the product is skipped, so theta = 0 gives the bits of theta == NULL).  The second
+ *   pass equalizes with it: wce_demodulate with h = H_dd, h_lt = NULL, WCE_DEMOD_TRACK.
+ *
+ *  - One launch serves both outputs; out->h alone never writes or re-reads x^ through memory,
+ *    and gives the bits the call with both outputs gives.
+ *  - A non-finite rx or theta makes the affected entries of H_dd non-finite (a theta all 53 of
+ *    them but DC); no other frame changes by a bit.  A frame's result depends only on its own
+ *    data and the call's arguments.
+ *  - Asynchronous on `stream`; reads nothing back and allocates nothing; the ctx only selects
+ *    the device: decode, re-encode and the second demodulation queue on one stream with no
+ *    host hop.
+ *  - WCE_EINVAL (text in wce_last_error()) before any launch: a NULL ctx, p, out or p->bits;
+ *    both outputs NULL; out->h without in or in->rx; in given with in->n_frames != n_frames; an
+ *    unknown modulation or rate; scale not positive and finite; bits_stride < ceil(T / 8);
+ *    tx_block_stride < 53 or, with more than one frame, tx_frame_stride < 14 tx_block_stride +
+ *    53 (with out->tx), likewise the frames' own strides (with in); h_stride < 53 (with out->h);
+ *    out->tx, out->h, in->rx or in->tx not 16-byte aligned; theta not 8-byte aligned; n_frames
+ *    < 0 or > 2^31 - 1.  n_frames == 0 is WCE_OK. */
+typedef struct {
+    const uint8_t *bits;      /* device; wce_viterbi_decode's packed bits: bits[f*bits_stride + (t>>3)], bit t&7 */
+    int64_t bits_stride;      /* bytes, >= ceil(T/8); rows need no alignment */
+    int32_t modulation, rate; /* WCE_MOD_*, WCE_RATE_* */
+    double scale;             /* as wce_demod.scale */
+    const double *theta;      /* device, theta[f*15+b] as wce_demodulate writes it; NULL = 0 */
+} wce_reencode_par;
+typedef struct {              /* each pointer may be NULL = not wanted; not both */
+    wce_complex *tx;          /* tx[f*tx_frame_stride + b*tx_block_stride + k], k < 53 */
+    int64_t tx_frame_stride, tx_block_stride;
+    wce_complex *h;           /* h[f*h_stride + k]: the data-aided estimate */
+    int64_t h_stride;
+} wce_reencode_out;
+int wce_reencode(wce_ctx *ctx, const wce_reencode_par *p, const wce_frames *in, int64_t n_frames,
+                 const wce_reencode_out *out, void *stream);
+
 /* Non-finite guard.  The reference passes NaN/Inf through
  * silently: main.c's PS_MMSE returns NaN x 53 (main.c:148-212), a zero pilot
  * makes PS_* divide by zero (main.c:82-84), and its dimension checks only
