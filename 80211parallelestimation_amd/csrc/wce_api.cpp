@@ -28,6 +28,7 @@ struct wce_ctx {
     int cov_taps = 0;           // State::cov_taps | State::taps_contig << 1 (diagonal Rhh: the tap-domain forms)
     int cov_path = 0;           // wce_debug_set_cov_path: 0 auto, 1 dense, 2 low-rank
     int cus = 0;                // CU count of `device`, read once in wce_ctx_create_empty (launch shapes; never on the launch path)
+    int xcds = 1;               // XCD labels the dispatcher deals workgroups over: 8 on gfx950, else 1; read with cus
     bool r1_plain = false;      // State::acoef == 1.0 and a full State::xmask (every TEXTBOOK state): the rank-1 kernel's
                                 // build without mask and scale.  Set with `mode`, wherever the state comes from
     bool cm_on = false;         // State::cm_on: a constant-modulus operator is loaded (wce_ctx_set_modulus)
@@ -119,6 +120,12 @@ int wce_ctx_create_empty(wce_ctx **out, int device)
         delete c;
         return fail(WCE_EHIP, "hipDeviceGetAttribute(multiprocessor count)");
     }
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) {
+        delete c;
+        return fail(WCE_EHIP, "hipGetDeviceProperties");
+    }
+    c->xcds = std::strncmp(prop.gcnArchName, "gfx950", 6) == 0 ? wce::R1_HEAD_XCDS : 1;
     hipError_t e = hipMalloc(&c->d_state, sizeof(State));
     if (e != hipSuccess) { delete c; return hipfail(e, "hipMalloc(state)"); }
     e = hipMemset(c->d_state, 0, sizeof(State));
@@ -702,8 +709,8 @@ static int estimate_impl(wce_ctx *c, const wce_frames *in, const wce_outputs *ou
         break;
     case wce::SolveStep::RefPilots: rc = wce::launch_mmse_ref_pilots(st, sa, stream); break;
     case wce::SolveStep::RefLsElem: rc = wce::launch_ref_ls_elem(st, sa, la, false, stream); break;
-    case wce::SolveStep::Closed: rc = wce::launch_mmse_rank1(st, sa, false, c->cus, c->r1_plain, stream); break;
-    case wce::SolveStep::ClosedNt: rc = wce::launch_mmse_rank1(st, sa, true, c->cus, c->r1_plain, stream); break;
+    case wce::SolveStep::Closed: rc = wce::launch_mmse_rank1(st, sa, false, c->cus, c->xcds, c->r1_plain, stream); break;
+    case wce::SolveStep::ClosedNt: rc = wce::launch_mmse_rank1(st, sa, true, c->cus, c->xcds, c->r1_plain, stream); break;
     case wce::SolveStep::Factor: rc = wce::launch_mmse_factor(st, sa, r.form, stream); break;
     case wce::SolveStep::Fused: rc = wce::launch_mmse_solve_ls(st, sa, la, r.form, stream); break;
     }

@@ -297,8 +297,10 @@ int launch_mmse_factor(const State *st, const SolveArgs &a, SolveForm form, void
 // made (never on this path: plans replay it), which sizes the persistent grid.
 // plain: State::acoef is 1.0 and State::xmask is full (every TEXTBOOK state) -- a fact the context caches
 // when it takes its State, like cus; the default build then neither reads nor applies them.
-// WCE_VARIANT_R1 = 3..12 pick the launch shape, cache policy, prologue and build here
-int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, int cus, bool plain, void *stream);
+// nx: the device's XCD labels (8 on gfx950, else 1), cached like cus: where rank1_head_shape (wce_route.h) says
+// so, the launch runs mmse_rank1_head_kernel (wce_rank1_head.hip) instead, the same closed form and bits.
+// WCE_VARIANT_R1 = 3..19 pick the kernel, launch shape, cache policy, prologue and build here
+int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, int cus, int nx, bool plain, void *stream);
 // units one sweep of its persistent grid covers on a device of `cus` CUs (wce_debug_rank1_rows_per_sweep)
 int rank1_rows_per_sweep(int cus);
 // the same factorisation + LS family + equalization of each frame in one launch (C semantics, one block)
@@ -375,7 +377,7 @@ constexpr int WCE_VARIANT_R1 = 5;      // PS_MMSE with a rank-1 covariance (TEXT
                                       // and the fused mmse_solve_ls_kernel), 2 = the closed form with
                                       // nontemporal loads and stores; 0 and 2 bit-identical, 0 and 1 agree to
                                       // ~1e-11 (each within 1e-10 of the long double answer).
-                                      // 3..12 are the closed form to the route planner and are read by
+                                      // 3..19 are the closed form to the route planner and are read by
                                       // launch_mmse_rank1 alone: 3 = one unit per 16-lane row, the grid covers
                                       // the batch -- what 0 launches too, since the persistent grid measured
                                       // no faster (DESIGN s6), 4 = the grid capped at 3 workgroups (48 rows
@@ -390,7 +392,12 @@ constexpr int WCE_VARIANT_R1 = 5;      // PS_MMSE with a rank-1 covariance (TEXT
                                       // State::xmask and applies them, where 0 on a State with a = 1 and a full
                                       // mask (every TEXTBOOK State) runs the build without them, 12 = that
                                       // build with tx and rx loads alternating and the shared u last, where 0
-                                      // issues tx, u, rx row by row; all bit-identical to 0.  2, 5, 6 and 10
+                                      // issues tx, u, rx row by row, 13..19 = mmse_rank1_head_kernel where
+                                      // rank1_head_shape (wce_route.h) finds the launch eligible, the headline's:
+                                      // 13 = never, 14 / 15 / 16 = in workgroups of 64 / 128 / 256 threads, 17 /
+                                      // 18 / 19 = the same with neighbouring groups on one XCD; 0 runs 18 there
+                                      // (R1_VARIANT_ADOPTED) and a launch that is not eligible runs
+                                      // mmse_rank1_kernel as under 13; all bit-identical to 0.  2, 5, 6 and 10
                                       // run the general build whatever the State
 constexpr int WCE_VARIANT_COUNT = 6;
 int variant_value(int which);

@@ -3020,7 +3020,7 @@ constexpr int64_t LR_STAGE_FROM = 0;
 static int g_variant[WCE_VARIANT_COUNT] = {0, 2, 0, 0, 0, 0};
 int set_variant(int which, int value)
 {
-    if (which < 0 || which >= WCE_VARIANT_COUNT || value < 0 || value > 15) return WCE_EINVAL;
+    if (which < 0 || which >= WCE_VARIANT_COUNT || value < 0 || value > 31) return WCE_EINVAL;
     __atomic_store_n(&g_variant[which], value, __ATOMIC_RELAXED);
     return WCE_OK;
 }

@@ -46,79 +46,16 @@
 // the bounds test, and then every vector load of its first unit, one wait chain in front
 // of the arithmetic.  The headline's order is tx, the shared u, rx, each row's loads together;
 // the other builds alternate tx and rx and load u behind them.
-#include "wce_internal.h"
-#include "wce_device.h"
+//
+// The headline's own launch (shared u, not split, no per-frame noise, the build without mask and scale, default
+// policy, strides and batch that fit 32 bits) does not run this kernel by default: rank1_head_shape
+// (wce_route.cpp) hands it to mmse_rank1_head_kernel (wce_rank1_head.hip) -- the same loads, arithmetic
+// (wce_rank1_body.h) and bits in workgroups of 128 threads whose neighbours share an XCD.  WCE_VARIANT_R1 = 13
+// keeps it here, and every other launch runs here whatever the variant.
+#include "wce_rank1_body.h"
 
 namespace wce {
 
-// Plain IEEE products, sums and quotients, never contracted into FMAs: the
-// numpy transcription in tests/test_rank1_model.py rounds alike.
-__device__ __forceinline__ double2 r1_mul(double2 a, double2 b)
-{
-#pragma clang fp contract(off)
-    return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ double2 r1_add(double2 a, double2 b)
-{
-#pragma clang fp contract(off)
-    return make_double2(a.x + b.x, a.y + b.y);
-}
-
-// p_k = w_k u_k, the factor of g's terms that the covariance alone decides: |u_k|^2 for
-// w = conj(u).  With a shared u it stays in registers from unit to unit.
-__device__ __forceinline__ double2 rank1_p(double2 u, double2 w, bool cwg)
-{
-#pragma clang fp contract(off)
-    return cwg ? r1_mul(w, u) : make_double2(u.x * u.x + u.y * u.y, 0.0);
-}
-
-// s of one unit.  Lane i of the unit's 16-lane row holds subcarriers i + 16 m
-// in x, r (rx), u, w and p (rank1_p); entries past subcarrier 52 (and x off
-// State::xmask) are zero.  cwg: w was given (SolveArgs::cw) -- g may be complex;
-// otherwise w = conj(u) and g = a sum |x|^2 |u|^2 is real.  Every lane returns the same bits.
-template <bool PLAIN>
-__device__ __forceinline__ double2 rank1_s(const double2 (&x)[4], const double2 (&r)[4], const double2 (&u)[4],
-                                           const double2 (&w)[4], const double2 (&p)[4], bool cwg, double ac,
-                                           double bc)
-{
-#pragma clang fp contract(off)
-    double2 g = make_double2(0.0, 0.0), q = g;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const double x2 = x[m].x * x[m].x + x[m].y * x[m].y;
-        const double ax2 = PLAIN ? x2 : ac * x2;
-        const double2 gk = make_double2(ax2 * p[m].x, ax2 * p[m].y);    // be_k al_k = a |x_k|^2 w_k u_k
-        const double2 qk = r1_mul(r1_mul(w[m], cconj(x[m])), r[m]);     // be_k rx_k
-        g = m ? r1_add(g, gk) : gk;
-        q = m ? r1_add(q, qk) : qk;
-    }
-    g = row16_sum(g);
-    q = row16_sum(q);
-    const double2 d = make_double2(bc + g.x, g.y);
-    double2 t;
-    if (cwg) {
-        const double den = d.x * d.x + d.y * d.y;
-        t = make_double2((q.x * d.x + q.y * d.y) / den, (q.y * d.x - q.x * d.y) / den);
-    } else {
-        t = make_double2(q.x / d.x, q.y / d.x);
-    }
-    double2 c = make_double2(0.0, 0.0);
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const double2 xu = r1_mul(x[m], u[m]);
-        const double2 at = r1_mul(PLAIN ? xu : make_double2(ac * xu.x, ac * xu.y), t);   // al_k t
-        const double2 rho = make_double2(r[m].x - at.x, r[m].y - at.y);
-        const double ti = 2.0 * x[m].y;                                      // x - conj x = (0, 2 Im x)
-        const double2 ck = r1_mul(w[m], make_double2(-(ti * rho.y), ti * rho.x));
-        c = m ? r1_add(c, ck) : ck;
-    }
-    c = row16_sum(c);
-    return make_double2(t.x + c.x / bc, t.y + c.y / bc);
-}
-
-// Workgroups resident per CU, and so per CU of the persistent grid: 4 waves per SIMD at up to 128
-// VGPRs, the occupancy every instantiation is held to (DESIGN s6 lists each one's registers).
-constexpr int R1_WG_PER_CU = 4;
 // cache policy of the tx / rx loads and the H stores (A/B, WCE_VARIANT_R1 = 2, 5, 6)
 constexpr int R1_POL_DEFAULT = 0, R1_POL_NT = 1, R1_POL_NT_STORES = 2, R1_POL_NT_LOADS = 3;
 // the default cache policy behind the previous prologue (A/B, WCE_VARIANT_R1 = 10): u and the State scalars
@@ -211,17 +148,9 @@ __global__ __launch_bounds__(256, R1_WG_PER_CU) void mmse_rank1_kernel(const Sta
         const int b = SPLIT ? (int)(gu - f * (uint32_t)a.nblk) : 0;
         const int64_t base = (int64_t)f * a.fs + (int64_t)(a.blk + b) * a.bs + lane_again(i);
         if (TXF) {
-            if (part != 2) {
-#pragma unroll
-                for (int m = 0; m < 3; ++m) xl[m] = ld2(a.tx, base + 16 * m);
-                xl[3] = zero;
-                if (i < NSC - 48) xl[3] = ld2(a.tx, base + 48);
-            }
+            if (part != 2) r1_fetch_row(a.tx, base, i, xl);
             if (part != 1) {
-#pragma unroll
-                for (int m = 0; m < 3; ++m) rl[m] = ld2(a.rx, base + 16 * m);
-                rl[3] = zero;
-                if (i < NSC - 48) rl[3] = ld2(a.rx, base + 48);
+                r1_fetch_row(a.rx, base, i, rl);
                 if (NOISE) bc = a.ow2[f];
             }
             return;
@@ -288,10 +217,7 @@ __global__ __launch_bounds__(256, R1_WG_PER_CU) void mmse_rank1_kernel(const Sta
         // tx, the shared u, rx: loads only, and conj(u) and |u|^2 behind the last of them -- a sign flip beside
         // the lane-masked u load would wait for tx and u inside its branch, ahead of the first rx load
         fetch(g, xc, rc, bc, 1);
-#pragma unroll
-        for (int m = 0; m < 3; ++m) u[m] = ld2(a.cu, i + 16 * m);
-        u[3] = zero;
-        if (i < NSC - 48) u[3] = ld2(a.cu, i + 48);
+        r1_fetch_row(a.cu, i, i, u);
         fetch(g, xc, rc, bc, 2);
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
@@ -400,7 +326,9 @@ static void launch_r1_pol(const State *st, const SolveArgs &a, const R1Shape &h,
     }
 }
 
-int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, int cus, bool plain, void *stream)
+void launch_mmse_rank1_head(const State *st, const SolveArgs &a, const R1HeadShape &h, void *stream);
+
+int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, int cus, int nx, bool plain, void *stream)
 {
     if (!a.cu) return WCE_EINVAL;
     if (a.split ? !a.dots : !a.w) return WCE_EINVAL;
@@ -409,11 +337,19 @@ int launch_mmse_rank1(const State *st, const SolveArgs &a, bool nt, int cus, boo
     if (a.ow2 && a.cw) return WCE_EINVAL;   // per-frame noise: TEXTBOOK only (check_route_facts), so w = conj(u)
     const int64_t units = a.split ? a.n * a.nblk : a.n;
     if (units > 0x7fffffffll) return WCE_EINVAL;
-    // the launch shape and the A/B builds (WCE_VARIANT_R1 = 3..12) are this launcher's alone: to the route
+    // the launch shape and the A/B builds (WCE_VARIANT_R1 = 3..19) are this launcher's alone: to the route
     // planner they are the closed form.  The build without mask and scale exists under the default cache
     // policy only (with a shared u: loads row by row, unless 12): the A/B policies (2, 5, 6, 10) run the
     // general build whatever the State, and 11 runs it under the default policy
     const int shape = variant_value(WCE_VARIANT_R1);
+    // mmse_rank1_head_kernel (wce_rank1_head.hip) where rank1_head_shape says so: the headline's launch, under
+    // variant 0 if a head shape was adopted and under 14..19; 13 is variant 0 without it
+    const R1HeadShape head = rank1_head_shape(
+        R1HeadFacts{a.cs == 0 && !a.cw, a.split != 0, a.ow2 != nullptr, a.cw != nullptr, plain, nt, shape, a.fs, a.ws, a.n}, nx);
+    if (head.threads) {
+        launch_mmse_rank1_head(st, a, head, stream);
+        return hipGetLastError() == hipSuccess ? WCE_OK : WCE_EHIP;
+    }
     const int rpw = shape == 8 ? 4 : shape == 9 ? 8 : 16;   // rows per workgroup: the kernel reads blockDim.x
     int64_t wgs = (units + rpw - 1) / rpw;   // one unit per row: the default, and what a batch below one sweep gets anyway
     const bool looping = shape == 4 || shape == 7;

@@ -123,7 +123,37 @@ int route_names(const Route &r, char *buf, size_t cap)
     return (int)s.size();
 }
 
+R1HeadShape rank1_head_shape(const R1HeadFacts &f, int nx)
+{
+    const R1HeadShape old{0, false};
+    if (!f.shared || f.split || f.noise || f.cw || !f.plain || f.nt) return old;
+    // the kernel's strides and row index are 32-bit values
+    if (f.fs < 0 || f.fs > 0xffffffffll || f.ws < 0 || f.ws > 0xffffffffll || f.n > 0x7fffffffll) return old;
+    const int v = f.variant == 0 ? R1_VARIANT_ADOPTED : f.variant;
+    if (v < R1_VARIANT_HEAD_FIRST || v > R1_VARIANT_HEAD_LAST) return old;   // 1..13: mmse_rank1_kernel's own shapes
+    const int k = (v - R1_VARIANT_HEAD_FIRST) % 3;
+    return R1HeadShape{64 << k, v >= R1_VARIANT_HEAD_FIRST + 3 && nx == R1_HEAD_XCDS};
+}
+
 }  // namespace wce
+
+extern "C" int wce_debug_rank1_head(int shared, int split, int noise, int cw, int plain, int nt, int variant,
+                                    long long fs, long long ws, long long n, int nx, int *remap)
+{
+    const wce::R1HeadFacts f{shared != 0, split != 0, noise != 0, cw != 0, plain != 0, nt != 0, variant, fs, ws, n};
+    const wce::R1HeadShape h = wce::rank1_head_shape(f, nx);
+    if (remap) *remap = h.remap;
+    return h.threads;
+}
+
+extern "C" int wce_debug_rank1_head_groups(unsigned groups, unsigned nx, unsigned *out, unsigned cap)
+{
+    if (!groups || !nx || groups > 0x7fffffffu || nx > 64) return WCE_EINVAL;
+    const unsigned per = (groups + nx - 1) / nx, grid = nx * per;
+    if (!out || cap < grid) return WCE_EINVAL;
+    for (unsigned b = 0; b < grid; b++) out[b] = wce::rank1_head_group(b, nx, per);
+    return (int)grid;
+}
 
 extern "C" int wce_debug_route(int mode, int bdot, int fuse, int cm, int lr_k0, int cov_rank, int semantics,
                                unsigned mask, int ls_f32, int r1, int ref_fc, int ref_ls, char *buf, size_t cap)

@@ -75,4 +75,41 @@ Route plan_route(const RouteFacts &f);
 // (wce_debug_route); returns the length, or -1 if it does not fit in cap
 int route_names(const Route &r, char *buf, size_t cap);
 
+// ---- the closed form's two kernels.  To plan_route() both are SolveStep::Closed; launch_mmse_rank1 asks
+// rank1_head_shape() which of them one launch runs, and nothing else decides it.
+// mmse_rank1_head_kernel (wce_rank1_head.hip) serves the headline's launch alone: its arguments are scalars that
+// arrive preloaded in SGPRs, the strides and the batch as 32-bit values.
+struct R1HeadFacts {
+    bool shared;       // one u for every unit (SolveArgs::cs == 0)
+    bool split;        // MATLAB averaging
+    bool noise;        // per-frame ow2
+    bool cw;           // a given w
+    bool plain;        // State::acoef == 1 and a full State::xmask
+    bool nt;           // the nontemporal build was asked for (SolveStep::ClosedNt)
+    int variant;       // WCE_VARIANT_R1
+    int64_t fs, ws, n; // frame stride, H row stride (complex elements), frames
+};
+struct R1HeadShape {
+    int threads;       // 64, 128 or 256 per workgroup; 0: mmse_rank1_kernel runs
+    bool remap;        // neighbouring groups share an XCD (rank1_head_group with nx > 1)
+};
+// WCE_VARIANT_R1 values that name the head kernel's shapes: 13 = never the head kernel, 14 / 15 / 16 = 64 / 128 /
+// 256 threads with groups in dispatch order, 17 / 18 / 19 = the same with neighbouring groups on one XCD
+constexpr int R1_VARIANT_HEAD_OFF = 13, R1_VARIANT_HEAD_FIRST = 14, R1_VARIANT_HEAD_LAST = 19;
+// what variant 0 launches where the head kernel is eligible: 128 threads, neighbours on one XCD -- the shape that
+// beat 13 at 65,536 frames and was not slower at 1,048,576 (DESIGN s6, profiles/rank1s_ab_*)
+constexpr int R1_VARIANT_ADOPTED = 18;
+// nx: XCD labels of the device: R1_HEAD_XCDS on gfx950, the count the kernel's remap is built for; 1 elsewhere: no remap
+constexpr int R1_HEAD_XCDS = 8;
+R1HeadShape rank1_head_shape(const R1HeadFacts &f, int nx);
+
+// Workgroup b of the head kernel's grid -> the group of rows it serves.  The dispatcher hands workgroup b to XCD
+// b % nx; with G groups and per = ceil(G / nx), XCD x gets the groups x per .. x per + per - 1, neighbours in
+// memory, so that an H line two groups share is written from one L2.  The grid is nx per workgroups; a result
+// >= G has no rows.  A bijection of [0, nx per), so every group is served once: placement changes no bit.
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline uint32_t rank1_head_group(uint32_t b, uint32_t nx, uint32_t per) { return (b % nx) * per + b / nx; }
+
 }  // namespace wce

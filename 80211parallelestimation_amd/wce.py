@@ -131,6 +131,8 @@ ABI = {
     "wce_debug_set_flat_chunk": [ctypes.c_int64],
     "wce_debug_set_variant": [c_int, c_int],
     "wce_debug_rank1_rows_per_sweep": [c_void_p],
+    "wce_debug_rank1_head": [c_int] * 7 + [c_int64] * 3 + [c_int, POINTER(c_int)],
+    "wce_debug_rank1_head_groups": [c_uint32, c_uint32, POINTER(c_uint32), c_uint32],
     "wce_debug_set_cov_path": [c_void_p, c_int],
     "wce_debug_lr_kernel": [c_void_p, c_int64],
     "wce_debug_route": [c_int] * 7 + [c_uint32] + [c_int] * 4 + [ctypes.c_char_p, c_size_t],

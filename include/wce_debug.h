@@ -60,7 +60,7 @@ int wce_debug_set_flat_chunk(long long frames);
  * also asks for LS outputs or equalization runs the LS pass, then this kernel;
  * 1 = the 53 x 53 factorisation, mmse_solve_fc_kernel, one wave per (frame,
  * block), and with LS outputs the fused mmse_solve_ls_kernel; 2 = the closed
- * form with nontemporal loads and stores; 3..12 are launch shapes, cache
+ * form with nontemporal loads and stores; 3..19 are launch shapes, cache
  * policies and builds of the closed form, the same route as 0 and read by its launcher
  * alone: 3 = one unit per 16-lane row, the grid covers the batch, so no row
  * loops and nothing is prefetched -- the shape 0 launches too; 4 = the grid
@@ -75,10 +75,12 @@ int wce_debug_set_flat_chunk(long long frames);
  * reads State::acoef and State::xmask and applies them -- on a State with
  * a = 1 and a full mask (every TEXTBOOK State) 0 runs a build without them;
  * 12 = that build with tx and rx loads alternating and the shared u last,
- * where 0 issues tx, u and rx row by row).
+ * where 0 issues tx, u and rx row by row; 13..19 = mmse_rank1_head_kernel,
+ * the headline launch's kernel with preloaded scalar arguments, switched off
+ * (13) or in one of its six shapes: wce_debug_rank1_head below).
  * Process-wide; the variants of which 0, 1, 2, 4 give bit-identical results,
  * which 3's kernels sum in different orders and agree to rounding (tests
- * check both); which 5's 0 and 2..12 are bit-identical, 0 and 1 agree to ~1e-11
+ * check both); which 5's 0 and 2..19 are bit-identical, 0 and 1 agree to ~1e-11
  * (both within 1e-10 of the long double closed form).  (Round 4 retired ls_flat_kernel -- which 1 = 0, 1 -- and the
  * REF frame tiles -- which 0 = 1.) */
 int wce_debug_set_variant(int which, int value);
@@ -88,6 +90,20 @@ int wce_debug_set_variant(int which, int value);
  * batch makes every 16-lane row loop; a smaller one launches one unit per
  * row.  Negative: an error code. */
 int wce_debug_rank1_rows_per_sweep(struct wce_ctx *ctx);
+/* Which of the closed form's two kernels one launch runs, as launch_mmse_rank1 decides it from these facts:
+ * a shared u, MATLAB split, per-frame noise, a given w, a State with a = 1 and a full mask, the nontemporal
+ * build asked for, the value of which 5, the frame and H row strides in complex elements, the frames and the
+ * device's XCD labels.  Returns the threads per workgroup of mmse_rank1_head_kernel (64, 128 or 256), whose
+ * arguments are preloaded scalars with 32-bit strides, or 0 for mmse_rank1_kernel; *remap (may be NULL) says
+ * whether neighbouring groups are placed on one XCD.  which 5 = 13 never runs the head kernel, 14 / 15 / 16 run
+ * it in workgroups of 64 / 128 / 256 threads in dispatch order, 17 / 18 / 19 the same with the remap; 0 runs
+ * what was adopted.  All bit-identical to 0.  Needs no device. */
+int wce_debug_rank1_head(int shared, int split, int noise, int cw, int plain, int nt, int variant, long long fs,
+                         long long ws, long long n, int nx, int *remap);
+/* The head kernel's placement of `groups` groups of rows over nx XCD labels: out[b] is the group that
+ * workgroup b serves, b < the returned grid size nx * ceil(groups / nx); an entry >= groups has no rows.
+ * WCE_EINVAL for no groups, no labels or a short buffer. */
+int wce_debug_rank1_head_groups(unsigned groups, unsigned nx, unsigned *out, unsigned cap);
 /* The kernel families one wce_estimate call launches, in order, as the route
  * planner (csrc/wce_route.h) decides them from these facts: the context's mode,
  * border dot and fusion switches, cm (a constant-modulus operator loaded and

@@ -6,8 +6,11 @@ rank1: the TEXTBOOK headline under WCE_VARIANT_R1 (0 closed form, 1 factorisatio
 3 one unit per row like 0, 4 three workgroups, 5 nontemporal stores, 6 nontemporal loads, 7 persistent grid with
 prefetch, 8 / 9 workgroups of 64 / 128 threads, 10 the previous prologue: u before tx / rx, 11 the general build
 that reads and applies State::acoef and State::xmask, 12 the build without them with tx / rx loads alternating
-and u last, where 0 loads tx, u, rx row by row); 0 and 2..12 are
-bit-identical, 1 agrees to rounding."""
+and u last, where 0 loads tx, u, rx row by row, 13 mmse_rank1_head_kernel off, 14 / 15 / 16 that kernel
+(preloaded scalar arguments) in workgroups of 64 / 128 / 256 threads, 17 / 18 / 19 the same with neighbouring
+groups on one XCD); 0 and 2..19 are bit-identical, 1 agrees to rounding.
+A variant named twice is timed twice per round, each copy on its own line: an A/A pair, whose difference is
+what the run cannot resolve."""
 import argparse
 import importlib
 import os
@@ -81,14 +84,14 @@ def main():
         run = lambda: ctx.estimate(fr, o, wce.LT_LS | wce.PS_LINEAR, s)
         alg, unit = bench.BYTES_LS_CFG2, "alg"
     ref_out = None
-    times = {v: [] for v in args.variants}
+    times = [[] for _ in args.variants]
     for r in range(args.rounds):
-        for v in args.variants:
+        for k, v in enumerate(args.variants):
             assert lib.wce_debug_set_variant(WHICH[args.leg], v) == 0
             for _ in range(3):
                 run()
             t = bench.time_events(wce, stream, run, args.reps)
-            times[v].append(t)
+            times[k].append(t)
             if r == 0:
                 got = [x.numpy() for x in outs]
                 if ref_out is None:
@@ -110,9 +113,9 @@ def main():
         print(f"same traffic shape, PS_Linear alone (ls_elem_kernel): median {t * 1e3:.1f} us  "
               f"{(bench.BYTES_PILOT_SECTORS + N * 16) * n / (t * 1e-3) / 1e12:.2f} TB/s on the sector floor "
               f"({', '.join(f'{x * 1e3:.0f}' for x in tl)})")
-    for v, ts in times.items():
+    for v, ts in zip(args.variants, times):
         t = float(np.median(ts))
-        print(f"{args.leg} variant {v}: median {t * 1e3:.1f} us  min {min(ts) * 1e3:.1f}  "
+        print(f"{args.leg} variant {v}: median {t * 1e3:.2f} us  min {min(ts) * 1e3:.2f}  "
               f"{alg * n / (t * 1e-3) / 1e12:.2f} TB/s {unit}  ({', '.join(f'{x * 1e3:.2f}' for x in ts)})")
 
 

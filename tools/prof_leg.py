@@ -4,8 +4,9 @@ workload for rocprofv3 --pmc passes (tools/pmc_legs.sh), so that a per-kernel
 average over the dispatches of a pass is an average over same-size launches.
 
 legs (bench.py field -> kernel, frames per launch):
-  headline   roofline            mmse_rank1_kernel<5, false, true, false, false, true>  65,536 (TEXTBOOK closed form, 16 lanes/frame:
-                                 loads row by row, no per-frame noise, shared u, not split, no prefetch, no mask and scale)
+  headline   roofline            mmse_rank1_head_kernel<128, true>  65,536 (TEXTBOOK closed form, 16 lanes/frame: what
+                                 WCE_VARIANT_R1 = 0 launches there -- preloaded scalar arguments, workgroups of 128
+                                 threads, neighbouring groups on one XCD; --variant and --frames pick another launch)
   apply      apply_kernel        apply_kernel                     65,536 (COV H = C W, persistent since round 5)
   cov_solve  cov_mode            mmse_solve_kernel<false>         65,536 (COV dense solve)
   ref        ref_mode.b1048576   mmse_ref_elem_kernel          1,048,576 (REF, main.c semantics)
@@ -34,7 +35,7 @@ sys.path.insert(0, REPO)
 N, NBLK = 53, 15
 
 LEGS = {
-    "headline": ("mmse_rank1_kernel<5, false, true, false, false, true>", 65536),   # the closed-form rank-1 solve (wce_rank1.hip)
+    "headline": ("mmse_rank1_head_kernel<128, true>", 65536),   # the closed-form rank-1 solve (wce_rank1_head.hip)
     "apply": ("apply_kernel", 65536),                # round 5: the streaming kernel at every size
     "apply1m": ("apply_kernel", 1 << 20),             # the same at configs[3]'s batch
     "cov_solve": ("mmse_solve_kernel<false>", 65536),
@@ -81,12 +82,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--leg", choices=sorted(LEGS), required=True)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--variant", type=int, default=0, help="headline: WCE_VARIANT_R1 of the launches")
+    ap.add_argument("--frames", type=int, default=0, help="headline: frames per launch, where not the bench's")
     args = ap.parse_args()
     wce = importlib.import_module("80211parallelestimation_amd")
     import bench
     inp = dict(np.load(os.path.join(REPO, "tests", "golden", "inputs_h.npz")))
     leg = args.leg
     n = LEGS[leg][1]
+    if leg == "headline":
+        n = args.frames or n
+        assert wce.load().wce_debug_set_variant(5, args.variant) == 0
     if leg in ("headline", "apply", "apply1m", "cov_solve"):
         if leg == "headline":
             ctx = wce.Context(inp["tx_pre"], inp["rx_pre"], inp["ow2"], wce.MMSE_TEXTBOOK)
