@@ -1205,6 +1205,118 @@ int wce_reencode(wce_ctx *c, const wce_reencode_par *p, const wce_frames *in, in
     return rc ? fail(rc, "reencode launch") : WCE_OK;
 }
 
+// ---------------------------------------------------------------- transmitter and channel
+static bool misaligned(const void *p, uintptr_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
+
+// the symbol side of wce_modulate and wce_transmit; null when it holds, else what is wrong
+static const char *check_symbols(const wce_complex *tx_pre, int64_t pre_stride, const wce_complex *sym,
+                                 int64_t frame_stride, int64_t block_stride, int32_t n_blocks, int64_t n_frames)
+{
+    if (n_blocks < 0 || n_blocks > wce::NBLK) return "n_blocks outside 0..15";
+    if (!tx_pre && n_blocks == 0) return "no field and n_blocks == 0";
+    if (n_blocks > 0 && !sym) return "sym required";
+    if (n_frames < 0 || n_frames > 0x7fffffffll) return "n_frames < 0 or > 2^31 - 1";
+    if (n_blocks > 0 && block_stride < wce::NSC) return "block_stride < 53";
+    if (n_blocks > 0 && n_frames > 1 && frame_stride < (int64_t)(n_blocks - 1) * block_stride + wce::NSC)
+        return "frame_stride < (n_blocks - 1) block_stride + 53";
+    if (tx_pre && pre_stride != 0 && pre_stride < wce::NSC) return "pre_stride neither 0 nor >= 53";
+    if (misaligned(tx_pre, 16) || misaligned(sym, 16)) return "tx_pre or sym not 16-byte aligned";
+    return nullptr;
+}
+
+// p and the capture side of wce_channel and wce_transmit
+static const char *check_channel(const wce_channel_par *p, const wce_complex *capture, int64_t capture_stride,
+                                 int64_t capture_len, int64_t n_frames)
+{
+    if (!p || !capture) return "null parameters or capture";
+    if (n_frames < 0 || n_frames > 0x7fffffffll) return "n_frames < 0 or > 2^31 - 1";
+    if (p->n_taps < 1 || p->n_taps > 16) return "n_taps outside 1..16";
+    if (p->taps && p->taps_stride != 0 && p->taps_stride < p->n_taps) return "taps_stride neither 0 nor >= n_taps";
+    if (capture_len < 1 || capture_len > 0x7fffffffll) return "capture_len < 1 or >= 2^31";
+    if (capture_stride < capture_len) return "capture_stride < capture_len";
+    if (misaligned(p->taps, 16) || misaligned(capture, 16)) return "taps or capture not 16-byte aligned";
+    if (misaligned(p->cfo, 8) || misaligned(p->ow2, 8)) return "cfo or ow2 not 8-byte aligned";
+    if (misaligned(p->delay, 4)) return "delay not 4-byte aligned";
+    return nullptr;
+}
+
+static void tx_symbols(wce::TxArgs &a, const wce_complex *tx_pre, int64_t pre_stride, const wce_complex *sym,
+                       int64_t frame_stride, int64_t block_stride, int32_t n_blocks)
+{
+    a.pre = reinterpret_cast<const double *>(tx_pre); a.pre_stride = pre_stride;
+    a.sym = reinterpret_cast<const double *>(sym); a.fs = frame_stride; a.bs = block_stride;
+    a.nb = n_blocks; a.field = tx_pre ? 1 : 0;
+}
+
+static void tx_channel(wce::TxArgs &a, const wce_channel_par *p, int field, wce_complex *capture,
+                       int64_t capture_stride, int64_t capture_len)
+{
+    a.taps = reinterpret_cast<const double *>(p->taps); a.ts = p->taps_stride;
+    a.nt = p->taps ? p->n_taps : 1;
+    a.chan_field = field;
+    a.cfo = p->cfo; a.ow2 = p->ow2; a.delay = p->delay; a.seed = p->seed; a.first = p->first_frame;
+    a.out = reinterpret_cast<double *>(capture); a.os = capture_stride; a.olen = capture_len;
+}
+
+int wce_modulate(wce_ctx *c, const wce_complex *tx_pre, int64_t pre_stride, const wce_complex *sym,
+                 int64_t frame_stride, int64_t block_stride, int32_t n_blocks, int64_t n_frames, wce_complex *wave,
+                 int64_t wave_stride, void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    if (!wave) return fail(WCE_EINVAL, "wce_modulate: wave required");
+    const char *bad = check_symbols(tx_pre, pre_stride, sym, frame_stride, block_stride, n_blocks, n_frames);
+    if (bad) return fail(WCE_EINVAL, (std::string("wce_modulate: ") + bad).c_str());
+    if (wave_stride < (tx_pre ? 160 : 0) + 80 * (int64_t)n_blocks)
+        return fail(WCE_EINVAL, "wce_modulate: wave_stride < the waveform's length");
+    if (misaligned(wave, 16)) return fail(WCE_EINVAL, "wce_modulate: wave not 16-byte aligned");
+    if (n_frames == 0) return WCE_OK;
+    wce::TxArgs a{};
+    tx_symbols(a, tx_pre, pre_stride, sym, frame_stride, block_stride, n_blocks);
+    a.out = reinterpret_cast<double *>(wave); a.os = wave_stride; a.n = n_frames;
+    DeviceGuard g(c->device);
+    const int rc = wce::launch_modulate(a, stream);
+    return rc ? fail(rc, "modulate launch") : WCE_OK;
+}
+
+int wce_channel(wce_ctx *c, const wce_complex *wave, int64_t wave_stride, int64_t wave_len, int64_t n_frames,
+                const wce_channel_par *p, wce_complex *capture, int64_t capture_stride, int64_t capture_len,
+                void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    if (!wave) return fail(WCE_EINVAL, "wce_channel: wave required");
+    const char *bad = check_channel(p, capture, capture_stride, capture_len, n_frames);
+    if (bad) return fail(WCE_EINVAL, (std::string("wce_channel: ") + bad).c_str());
+    if (wave_len < 1 || wave_len > 0x7fffffffll) return fail(WCE_EINVAL, "wce_channel: wave_len < 1 or >= 2^31");
+    if (wave_stride < wave_len) return fail(WCE_EINVAL, "wce_channel: wave_stride < wave_len");
+    if (misaligned(wave, 16)) return fail(WCE_EINVAL, "wce_channel: wave not 16-byte aligned");
+    if (n_frames == 0) return WCE_OK;
+    wce::TxArgs a{};
+    a.wave = reinterpret_cast<const double *>(wave); a.ws = wave_stride; a.wlen = wave_len; a.n = n_frames;
+    tx_channel(a, p, p->field ? 1 : 0, capture, capture_stride, capture_len);
+    DeviceGuard g(c->device);
+    const int rc = wce::launch_channel(a, stream);
+    return rc ? fail(rc, "channel launch") : WCE_OK;
+}
+
+int wce_transmit(wce_ctx *c, const wce_complex *tx_pre, int64_t pre_stride, const wce_complex *sym,
+                 int64_t frame_stride, int64_t block_stride, int32_t n_blocks, int64_t n_frames,
+                 const wce_channel_par *p, wce_complex *capture, int64_t capture_stride, int64_t capture_len,
+                 void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    const char *bad = check_symbols(tx_pre, pre_stride, sym, frame_stride, block_stride, n_blocks, n_frames);
+    if (!bad) bad = check_channel(p, capture, capture_stride, capture_len, n_frames);
+    if (bad) return fail(WCE_EINVAL, (std::string("wce_transmit: ") + bad).c_str());
+    if (n_frames == 0) return WCE_OK;
+    wce::TxArgs a{};
+    tx_symbols(a, tx_pre, pre_stride, sym, frame_stride, block_stride, n_blocks);
+    a.n = n_frames;
+    tx_channel(a, p, a.field, capture, capture_stride, capture_len);
+    DeviceGuard g(c->device);
+    const int rc = wce::launch_transmit(a, stream);
+    return rc ? fail(rc, "transmit launch") : WCE_OK;
+}
+
 // ---------------------------------------------------------------- runtime helpers
 int wce_device_count(int *count)
 {

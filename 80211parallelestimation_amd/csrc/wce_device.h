@@ -120,6 +120,15 @@ __device__ __forceinline__ double2 sum_over_p(double2 w)
     return make_double2(sum_xor32(sum_xor16(w.x)), sum_xor32(sum_xor16(w.y)));
 }
 
+// splitmix64's finaliser: the counter RNG of wce_synth_frames and wce_channel, keyed by (seed, frame, stream)
+__device__ __forceinline__ uint64_t mix64(uint64_t x)
+{
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
 // wave-local LDS ordering (one wave owns the buffer; no workgroup barrier)
 __device__ __forceinline__ void wave_lds_sync()
 {

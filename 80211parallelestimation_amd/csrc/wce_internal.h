@@ -274,6 +274,29 @@ struct ReencodeArgs {
     int64_t tfs, tbs, hs;
 };
 
+// transmitter and channel (wce_transmit.hip).  modulate reads pre / sym and writes the clean waveform to out;
+// channel reads wave and writes capture windows to out; transmit reads pre / sym and writes capture windows
+struct TxArgs {
+    const double *pre, *sym;      // pre null: no field (then field == 0); sym may be null when nb == 0
+    int64_t pre_stride, fs, bs;
+    int32_t nb, field;
+    const double *wave;           // channel only: wave[f*ws + m], m < wlen
+    int64_t ws, wlen;
+    double *out;                  // out[f*os + i], i < olen
+    int64_t os, olen;
+    const double *taps;           // null: one unit tap (nt == 1)
+    int64_t ts;
+    int32_t nt;
+    int32_t chan_field;           // 1: the time origin is the waveform's sample 160
+    const double *cfo, *ow2;
+    const int32_t *delay;
+    uint64_t seed;
+    int64_t first, n;
+};
+
+int launch_modulate(const TxArgs &a, void *stream);
+int launch_channel(const TxArgs &a, void *stream);
+int launch_transmit(const TxArgs &a, void *stream);
 int launch_ls(const State *st, const LsArgs &a, void *stream);
 int launch_demod(const DemodArgs &a, void *stream);
 int launch_demap(const DemapArgs &a, void *stream);

@@ -2899,13 +2899,7 @@ __global__ __launch_bounds__(256) void cm_cplx_kernel(const State *__restrict__ 
 // =====================================================================
 // Synthetic frames: splitmix64 counter RNG keyed by (seed, frame, stream).
 // =====================================================================
-__device__ __forceinline__ uint64_t mix64(uint64_t x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
+// (mix64: wce_device.h)
 __device__ __forceinline__ double u01(uint64_t h) { return (double)(h >> 11) * (1.0 / 9007199254740992.0); }
 // approximately N(0,1): Irwin-Hall of 4 uniforms, unit variance
 __device__ __forceinline__ double gauss(uint64_t key)

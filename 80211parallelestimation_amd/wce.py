@@ -112,6 +112,13 @@ class ReencodeOut(ctypes.Structure):
                 ("h_stride", c_int64)]
 
 
+class ChannelPar(ctypes.Structure):
+    """struct wce_channel_par (include/wce.h)."""
+    _fields_ = [("taps", c_void_p), ("taps_stride", c_int64), ("n_taps", c_int32), ("field", c_int32),
+                ("cfo", c_void_p), ("ow2", c_void_p), ("delay", c_void_p), ("seed", c_uint64),
+                ("first_frame", c_int64)]
+
+
 _lib = None
 
 # (name, argtypes) for every symbol include/wce.h and include/wce_compat.h declare
@@ -177,6 +184,12 @@ ABI = {
                            c_int64, c_void_p, c_int64, c_void_p, c_void_p],
     "wce_decode_info_bits": [c_int32, c_int32],
     "wce_reencode": [c_void_p, POINTER(ReencodePar), POINTER(Frames), c_int64, POINTER(ReencodeOut), c_void_p],
+    "wce_modulate": [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int64, c_void_p, c_int64,
+                     c_void_p],
+    "wce_channel": [c_void_p, c_void_p, c_int64, c_int64, c_int64, POINTER(ChannelPar), c_void_p, c_int64, c_int64,
+                    c_void_p],
+    "wce_transmit": [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int64, POINTER(ChannelPar),
+                     c_void_p, c_int64, c_int64, c_void_p],
     "wce_nonfinite_scan": [c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int64, c_uint32, c_void_p, c_void_p,
                            c_void_p],
     "wce_comm_unique_id": [c_void_p],
@@ -368,12 +381,14 @@ class Context:
         self.handle = c_void_p()
         self.device = device
         self.mode = MMSE_COV if Rhh is not None else mode
+        self.tx_pre = None
         if empty:
             _check(lib.wce_ctx_create_empty(byref(self.handle), device), "wce_ctx_create_empty")
             return
         tp, rp = _as_c128(tx_pre), _as_c128(rx_pre)
         if tp.shape != (NSC,) or rp.shape != (NSC,):
             raise ValueError("tx_pre / rx_pre must hold 53 subcarriers")
+        self.tx_pre = tp.copy()   # link_host transmits it
         if Rhh is not None:   # WCE_MMSE_COV: model channel covariance (53 x 53, time domain)
             R = _as_c128(Rhh)
             if R.shape != (NSC, NSC):
@@ -582,6 +597,181 @@ class Context:
                         tx_block_stride, _addr(h), h_stride)
         _check(_lib.wce_reencode(self.handle, byref(p), byref(frames) if frames is not None else None, n_frames,
                                  byref(o), stream), "wce_reencode")
+
+    def modulate(self, sym, n_frames, wave, n_blocks=NBLK, tx_pre=None, pre_stride=0, frame_stride=None,
+                 block_stride=NSC, wave_stride=None, stream=None):
+        """wce_modulate on device arrays: sym complex [n][n_blocks][block_stride] (53 bins a block, e.g. reencode's
+        tx) and, with tx_pre, the preamble's 53 bins ([53] shared with pre_stride 0, or [n][pre_stride]) -> wave
+        complex [n][wave_stride], the clean time-domain waveform: the 160-sample long training field (with
+        tx_pre), then 80 samples a block, cyclic prefix first.  The inverse of front_end_preamble / _blocks.  The
+        frame stride defaults to n_blocks block strides, the wave stride to the waveform's length."""
+        S = (160 if tx_pre is not None else 0) + SAMPLES_PER_BLOCK * n_blocks
+        _check(_lib.wce_modulate(self.handle, _addr(tx_pre), pre_stride, _addr(sym),
+                                 frame_stride if frame_stride is not None else n_blocks * block_stride, block_stride,
+                                 n_blocks, n_frames, _addr(wave), wave_stride if wave_stride is not None else S,
+                                 stream), "wce_modulate")
+
+    @staticmethod
+    def _channel_par(taps, n_taps, taps_stride, field, cfo, ow2, delay, seed, first_frame):
+        return ChannelPar(_addr(taps), taps_stride, n_taps, int(bool(field)), _addr(cfo), _addr(ow2), _addr(delay),
+                          seed, first_frame)
+
+    def channel(self, wave, n_frames, wave_len, capture, capture_len, taps=None, n_taps=1, taps_stride=0, field=True,
+                cfo=None, ow2=None, delay=None, seed=0x80211, first_frame=0, wave_stride=None, capture_stride=None,
+                stream=None):
+        """wce_channel on device arrays: wave complex [n][wave_stride] (modulate's) -> capture complex
+        [n][capture_stride], raw capture windows of capture_len samples: the waveform through the frame's n_taps
+        taps (complex [n_taps] shared with taps_stride 0, or [n][taps_stride]; None: one unit tap), turned by
+        exp(2 pi i cfo[f] n) (cfo float64 [n], cycles per sample; n counts from the end of the field when `field`),
+        placed delay[f] (int32 [n], any sign) samples into the window and clipped to it, plus CN(0, ow2[f])
+        Gaussian noise (ow2 float64 [n]) drawn from (seed, first_frame + f, sample).  The input of front_end_sync."""
+        p = self._channel_par(taps, n_taps, taps_stride, field, cfo, ow2, delay, seed, first_frame)
+        _check(_lib.wce_channel(self.handle, _addr(wave), wave_stride if wave_stride is not None else wave_len,
+                                wave_len, n_frames, byref(p), _addr(capture),
+                                capture_stride if capture_stride is not None else capture_len, capture_len, stream),
+               "wce_channel")
+
+    def transmit(self, sym, n_frames, capture, capture_len, n_blocks=NBLK, tx_pre=None, pre_stride=0,
+                 frame_stride=None, block_stride=NSC, taps=None, n_taps=1, taps_stride=0, cfo=None, ow2=None,
+                 delay=None, seed=0x80211, first_frame=0, capture_stride=None, stream=None):
+        """wce_transmit on device arrays: modulate and channel in one launch, the bits of the two calls in
+        sequence; the clean waveform never goes through memory.  Arguments as theirs; the field is there with
+        tx_pre."""
+        p = self._channel_par(taps, n_taps, taps_stride, tx_pre is not None, cfo, ow2, delay, seed, first_frame)
+        _check(_lib.wce_transmit(self.handle, _addr(tx_pre), pre_stride, _addr(sym),
+                                 frame_stride if frame_stride is not None else n_blocks * block_stride, block_stride,
+                                 n_blocks, n_frames, byref(p), _addr(capture),
+                                 capture_stride if capture_stride is not None else capture_len, capture_len, stream),
+               "wce_transmit")
+
+    def _transmit_device(self, dsym, B, n_blocks, dpre, pre_stride, taps, cfo, ow2, delay, capture_len, seed,
+                         first_frame, fused):
+        """transmit_host's device half: symbols (and the preamble) on the device, the channel's per-frame
+        parameters on the host -> (capture DeviceArray [B][capture_len], what the queued calls read until the
+        caller synchronises)"""
+        dtaps, n_taps, ts = None, 1, 0
+        if taps is not None:
+            taps = _as_c128(taps)
+            if taps.ndim not in (1, 2) or (taps.ndim == 2 and taps.shape[0] != B):
+                raise ValueError("taps must be [n_taps] or [B][n_taps] complex")
+            n_taps, ts = taps.shape[-1], (taps.shape[1] if taps.ndim == 2 else 0)
+            dtaps = DeviceArray.from_numpy(taps)
+
+        def per_frame(x, dtype):   # a scalar or [B] -> a device array [B]
+            if x is None:
+                return None
+            return DeviceArray.from_numpy(np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=dtype), (B,))))
+        dcfo, dow2, ddelay = per_frame(cfo, np.float64), per_frame(ow2, np.float64), per_frame(delay, np.int32)
+        S = (160 if dpre is not None else 0) + SAMPLES_PER_BLOCK * n_blocks
+        dcap = DeviceArray((B, capture_len), zero=True)
+        keep = [dtaps, dcfo, dow2, ddelay]
+        if fused:
+            self.transmit(dsym, B, dcap, capture_len, n_blocks, dpre, pre_stride, taps=dtaps, n_taps=n_taps,
+                          taps_stride=ts, cfo=dcfo, ow2=dow2, delay=ddelay, seed=seed, first_frame=first_frame)
+        else:
+            dwave = DeviceArray((B, S), zero=True)
+            keep.append(dwave)
+            self.modulate(dsym, B, dwave, n_blocks, dpre, pre_stride)
+            self.channel(dwave, B, S, dcap, capture_len, dtaps, n_taps, ts, dpre is not None, dcfo, dow2, ddelay,
+                         seed, first_frame)
+        return dcap, keep
+
+    def transmit_host(self, sym, tx_pre=None, taps=None, cfo=None, ow2=None, delay=None, capture_len=None,
+                      seed=0x80211, first_frame=0, fused=True):
+        """Convenience: host symbols sym [B][n_blocks][53] (n_blocks 0..15) and, optionally, the preamble's 53
+        bins tx_pre ([53] shared, or [B][53]) -> raw capture windows [B][capture_len] on the host.  taps [n_taps]
+        or [B][n_taps] complex (None: a unit tap); cfo (cycles per sample), ow2 (noise variance per complex
+        sample) and delay (int, any sign): a scalar or [B], None = 0.  capture_len defaults to the waveform's
+        length plus the taps' tail.  fused: one transmit launch, else modulate then channel -- the same bits."""
+        sym = _as_c128(sym)
+        if sym.ndim != 3 or sym.shape[2] != NSC or sym.shape[1] > NBLK:
+            raise ValueError("sym must be [B][n_blocks <= 15][53] complex")
+        B, n_blocks = sym.shape[0], sym.shape[1]
+        dpre, ps = None, 0
+        if tx_pre is not None:
+            tx_pre = _as_c128(tx_pre)
+            if tx_pre.shape not in ((NSC,), (B, NSC)):
+                raise ValueError("tx_pre must be [53] or [B][53] complex")
+            dpre, ps = DeviceArray.from_numpy(tx_pre), (NSC if tx_pre.ndim == 2 else 0)
+        dsym = DeviceArray.from_numpy(sym) if n_blocks else None
+        if capture_len is None:
+            capture_len = (160 if dpre is not None else 0) + SAMPLES_PER_BLOCK * n_blocks + \
+                (np.shape(taps)[-1] if taps is not None else 1) - 1
+        dcap, keep = self._transmit_device(dsym, B, n_blocks, dpre, ps, taps, cfo, ow2, delay, int(capture_len), seed,
+                                           first_frame, fused)
+        synchronize()
+        return dcap.numpy()
+
+    def link_host(self, modulation, rate, snr_db, n_frames, sources=(LT_LS, PS_LINEAR, PS_MMSE), taps=None, cfo=None,
+                  delay=None, capture_len=1488, threshold=0.25, backoff=0, seed=0x80211, dd_iterations=0,
+                  scale=8.8753):
+        """The experiment WiFi_RX.m:4-9 announces (SNR, channel_model, FO), for a batch, scored in coded bit
+        errors: n_frames packets of random information bits (drawn on the host from `seed`, the last six 0) are
+        re-encoded to symbols with 802.11's pilots, transmitted behind the context's tx preamble through `taps`
+        ([n_taps] or [B][n_taps], None: a unit tap; pdp_taps draws them), a carrier offset cfo and a delay (scalar
+        or [B]) with Gaussian noise at snr_db (scalar or [B]) into capture windows of capture_len samples, and
+        received: front_end_sync, the field with its own offset estimate, the blocks, estimate, and per source
+        (estimator bits) demodulate (tracked; blended with lt_ls for every source but LT_LS), soft_demap and
+        viterbi_decode against the sent bits.  Everything between the bits going up and the counts coming down
+        is queued on one stream; the capture never visits the host.
+        snr_db is nominal: ow2 = (52 scale^2 / 4096) / 10^(snr_db / 10), the mean power of a sample of a frame
+        of unit-mean-energy constellation points over the noise variance, for taps with sum |h|^2 = 1.  PS_MMSE
+        takes each frame's ow2 from it on a TEXTBOOK context (with the frame's own preamble as covariance), the
+        context's ow2 and covariance otherwise.
+        dd_iterations n > 0: n decision-directed rounds behind each source's decoder; its count is the last
+        round's.
+        -> {source: nbiterr uint32 [B]} plus "start" int32 [B] (-1: not detected; its counts are those of an
+        all-zero decode), "metric" [B], "cfo" [B] (the estimate), "ow2" [B] and "bits" uint8 [B][T]."""
+        B, T = int(n_frames), info_bits(modulation, rate)
+        if self.tx_pre is None:
+            raise ValueError("link_host needs a context built from a tx preamble")
+        names = {LT_LS: "lt_ls", PS_LINEAR: "ps_linear", PS_CUBIC: "ps_cubic", PS_SINC: "ps_sinc", PS_MMSE: "ps_mmse"}
+        sources = tuple(sources)
+        if not sources or any(s not in names for s in sources):
+            raise ValueError("sources must be estimator bits")
+        rng = np.random.default_rng(seed)
+        bits = rng.integers(0, 2, (B, T), dtype=np.uint8)
+        bits[:, T - 6:] = 0
+        ow2 = np.ascontiguousarray(np.broadcast_to(
+            (52.0 * scale * scale / 4096.0) / 10.0 ** (np.asarray(snr_db, np.float64) / 10.0), (B,)))
+        dbits = DeviceArray.from_numpy(np.packbits(bits, axis=1, bitorder="little"))
+        dtx = DeviceArray((B, NBLK, NSC), zero=True)
+        dpre = DeviceArray.from_numpy(self.tx_pre)
+        dfield = DeviceArray((160,), zero=True)   # the clean field: its samples 32..95 are one period, sync's ltf
+        self.reencode(dbits, B, modulation, rate, scale, tx=dtx)
+        self.modulate(None, 1, dfield, 0, dpre)
+        dcap, keep = self._transmit_device(dtx, B, NBLK, dpre, 0, taps, cfo, ow2, delay, int(capture_len), seed, 0,
+                                           True)
+        dstart, dmetric = DeviceArray((B,), np.int32, zero=True), DeviceArray((B,), np.float64, zero=True)
+        dow2e, dcfo = DeviceArray((B,), np.float64, zero=True), DeviceArray((B,), np.float64, zero=True)
+        drx, drxpre = DeviceArray((B, NBLK, NSC), zero=True), DeviceArray((B, NSC), zero=True)
+        self.front_end_sync(dcap, B, capture_len, dfield.addr + 32 * 16, threshold, backoff, dstart, dmetric)
+        self.front_end_preamble(dcap, B, capture_len, drxpre, dow2e, cfo=dcfo, start=dstart)
+        self.front_end_blocks(dcap, B, NBLK, drx, cfo=dcfo, start=dstart, capture_len=capture_len)
+        mask = LT_LS
+        for s in sources:
+            mask |= s
+        outs = {n: DeviceArray((B, NSC), zero=True) for bit, n in names.items() if mask & bit}
+        o = Outputs(*[(outs[n].addr if n in outs else None) for n in names.values()], None, NSC, NBLK * NSC, NSC,
+                    PS_LINEAR, 0)
+        fr = self.frames(dtx, drx, B, rx_pre=drxpre, tx_pre=dpre)
+        if mask & PS_MMSE and self.mode == MMSE_TEXTBOOK:
+            self.estimate(fr, o, mask | FRAME_COV, ow2=keep[2])
+        else:
+            self.estimate(fr, o, mask)
+        runs = {}
+        for s in sources:
+            h = outs[names[s]]
+            hlt = None if s == LT_LS else outs["lt_ls"]
+            dem = self._demod_device(fr, B, h, hlt, modulation, scale, True, True)
+            dec = self._decode_device(dem["eq"], h, hlt, B, modulation, rate, scale, True, bits)
+            dd = self._dd_device(fr, B, dec["bits"], dem["theta"], modulation, rate, scale, True, dec["_ref"],
+                                 int(dd_iterations)) if dd_iterations else None
+            runs[s] = (dem, dec, dd)
+        synchronize()
+        res = {s: (dd if dd is not None else dec)["nbiterr"].numpy() for s, (dem, dec, dd) in runs.items()}
+        res.update(start=dstart.numpy(), metric=dmetric.numpy(), cfo=dcfo.numpy(), ow2=ow2, bits=bits)
+        return res
 
     def _dd_device(self, fr, B, dbits, dtheta, modulation, rate, scale, terminated, dref, rounds):
         """queue `rounds` decision-directed passes behind a decode, on the same (null) stream with no host read:
@@ -1017,6 +1207,22 @@ class Plan:
             self.close()
         except Exception:  # pragma: no cover
             pass
+
+
+def pdp_taps(rng, n_frames, power) -> np.ndarray:
+    """Channel taps for Context.transmit_host / link_host from a power-delay profile: tap t of each of n_frames
+    frames is drawn CN(0, power[t]) from rng (a numpy Generator), and each frame's taps are then normalised to
+    sum |h|^2 = 1 -> complex [n_frames][len(power)], 1..16 taps.  np.diag(power), zero-padded to 53 x 53 (for a
+    profile that sums to 1), is the Rhh that Context(Rhh=...) takes, so a matched-model WCE_MMSE_COV run is
+        R = np.zeros((53, 53), complex); R[:len(power), :len(power)] = np.diag(power)
+        ctx = Context(tx_pre, rx_pre, ow2, Rhh=R)
+        ctx.link_host(modulation, rate, snr_db, B, taps=pdp_taps(rng, B, power))"""
+    power = np.asarray(power, np.float64)
+    if power.ndim != 1 or not 1 <= power.size <= 16 or np.any(power < 0) or not power.sum() > 0:
+        raise ValueError("power must hold 1..16 non-negative tap powers")
+    h = (rng.standard_normal((n_frames, power.size)) + 1j * rng.standard_normal((n_frames, power.size))) * \
+        np.sqrt(power / 2)
+    return h / np.sqrt(np.sum(np.abs(h) ** 2, axis=1, keepdims=True))
 
 
 def state_blob(tx_pre, rx_pre, ow2, mode=MMSE_REF, Rhh=None) -> np.ndarray:

@@ -275,7 +275,9 @@ int wce_mmse_apply(wce_ctx *ctx, const wce_complex *W, wce_complex *H, int64_t s
  * keyed by (seed, global frame index), so any shard regenerates identical
  * frames: BPSK data +-A, pilots A*(1,1,1,-1)*p_b (802.11 polarity), DC = 0,
  * a 6-tap exponential-PDP channel (or h_shared for every frame, if non-NULL),
- * CN(0, ow2) noise.  rx_pre (may be NULL) = per-frame preamble H*tx_pre + noise/sqrt2. */
+ * CN(0, ow2) noise.  rx_pre (may be NULL) = per-frame preamble H*tx_pre + noise/sqrt2.
+ * The noise is an Irwin-Hall sum of four uniforms (unit variance, no sample beyond 3.46 sigma): fine for
+ * timing and parity runs, not for error rates, which should draw theirs from wce_channel. */
 int wce_synth_frames(wce_ctx *ctx, wce_complex *tx, wce_complex *rx, wce_complex *rx_pre,
                      int64_t frame_stride, int64_t block_stride, int64_t pre_stride,
                      int64_t first_frame, int64_t n_frames, uint64_t seed,
@@ -615,6 +617,89 @@ typedef struct {              /* each pointer may be NULL = not wanted; not both
 } wce_reencode_out;
 int wce_reencode(wce_ctx *ctx, const wce_reencode_par *p, const wce_frames *in, int64_t n_frames,
                  const wce_reencode_out *out, void *stream);
+
+/* ---- transmitter and channel: symbols -> clean waveform -> raw capture windows (the
+ * reference's WiFi_RX.m:4-9 declares SNR, channel_model, FO and Pawgn and uses none of
+ * them: its input is one recorded capture) ----
+ * wce_reencode stops at the frequency-domain symbols.  These three calls take them to
+ * what an antenna would have recorded, on the device, so that wce_front_end_sync and the
+ * receive chain behind it run on as many packets as an error-rate experiment needs, at a
+ * chosen SNR, through a chosen multipath channel and carrier offset.
+ *
+ * wce_modulate is the inverse of wce_front_end_blocks / _preamble:
+ *   block     from 53 bins X[i]: Y[(i - 26) mod 64] = X[i], the other 11 bins 0;
+ *             y[n] = (1/64) sum_k Y[k] e^(+2 pi i k n / 64): MATLAB's ifft, the exact
+ *             inverse of circshift(fft(., 64), 26)(1:53).
+ *   field     present iff tx_pre != NULL; 160 samples: y[32..63], y, y of
+ *             tx_pre[f*pre_stride + i] (pre_stride == 0: one shared preamble).  y is computed
+ *             once: the two copies, and the prefix, are the same bits.
+ *   data      block b is 80 samples: y_b[48..63], y_b of sym[f*frame_stride + b*block_stride + i].
+ *   waveform  wave[f*wave_stride + m], m < S = 160 [field] + 80 n_blocks: the field, then
+ *             blocks 0 .. n_blocks - 1.  n_blocks == 0 with a field is allowed.
+ *   There is no spectral windowing: the recorded tx_packet has the first prefix sample of
+ *   every block, and of the field, shaped by a window; this call does not do that.
+ *
+ * wce_channel turns a clean waveform into a capture window.  s[m] = the waveform for m in
+ * [0, wave_len), 0 outside; frame f, window sample i < capture_len:
+ *   y[m] = sum_{t < n_taps, t ascending} h[f][t] s[m - t]       0 <= m < wave_len + n_taps - 1
+ *   r[m] = y[m] exp(+2 pi i cfo[f] n),   n = m - 160 field
+ *   capture[f][i] = w[f][i] + (r[i - delay[f]] if 0 <= i - delay[f] < wave_len + n_taps - 1, else 0)
+ *   time      the axis of wce_front_end_*_cfo: n = 0 at the packet's first sample after the
+ *             field.  The rotor is that call's exact-phase construction with the opposite sign
+ *             (the phase cfo n is reduced exactly before sincospi sees it); where cfo[f] == 0.0
+ *             the product is skipped.  A waveform that overhangs the window on either side is
+ *             clipped silently.
+ *   noise     exactly Gaussian, by Box-Muller on the counter RNG of wce_synth_frames:
+ *             key = mix64(seed ^ mix64(first_frame + f)), a = mix64(key ^ 2i), b = mix64(key ^ (2i + 1)),
+ *             u1 = ((a >> 11) + 1) 2^-53 in (0, 1], u2 = (b >> 11) 2^-53,
+ *             w = sqrt(ow2[f] / 2) sqrt(-2 ln u1) (cos 2 pi u2 + i sin 2 pi u2)
+ *             (mix64: splitmix64's finaliser, x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30)
+ *             0xBF58476D1CE4E5B9; x = (x ^ x >> 27) 0x94D049BB133111EB; x ^ x >> 31).
+ *             It depends on (seed, first_frame + f, i) only: shards regenerate identical windows,
+ *             and the same seed with another channel gives the same noise.  ow2[f] == 0 is
+ *             allowed: that frame gets no noise, as every frame does with ow2 == NULL.
+ *   guard     a frame whose ow2[f] is negative or not finite, whose cfo[f] or one of whose
+ *             taps is not finite, or whose waveform holds a non-finite sample gets NaN in every
+ *             sample of its window (so wce_front_end_sync gives it start = -1); no other frame
+ *             changes by a bit.  Padding beyond capture_len is never written.
+ *
+ * wce_transmit is both in one launch, bit-identical to wce_modulate followed by wce_channel
+ * on the same arguments (p->field is ignored: the field is present iff tx_pre != NULL), and
+ * the clean waveform never goes through memory.
+ *
+ *  - All three are asynchronous on `stream`, read nothing back and allocate nothing; the
+ *    ctx only selects the device.  A frame's bits depend only on its own data, its global
+ *    index first_frame + f and the call's arguments.
+ *  - WCE_EINVAL (text in wce_last_error()) before any launch: a NULL ctx, p, wave or capture;
+ *    sym NULL with n_blocks > 0; n_blocks outside 0..15; no field and n_blocks == 0; n_taps
+ *    outside 1..16; taps_stride neither 0 nor >= n_taps; with n_blocks > 0, block_stride < 53
+ *    or, with more than one frame, frame_stride < (n_blocks - 1) block_stride + 53; pre_stride
+ *    neither 0 nor >= 53; wave_stride < S, or < wave_len; capture_stride < capture_len;
+ *    capture_len or wave_len < 1 or >= 2^31; a complex pointer not 16-byte aligned; cfo or
+ *    ow2 not 8-byte aligned; delay not 4-byte aligned; n_frames < 0 or > 2^31 - 1.
+ *    n_frames == 0 is WCE_OK. */
+typedef struct {
+    const wce_complex *taps;  /* device; taps[f*taps_stride + t], t < n_taps; NULL = one unit tap */
+    int64_t taps_stride;      /* >= n_taps; 0 = one set shared by all frames */
+    int32_t n_taps;           /* 1..16 (within the 16-sample cyclic prefix) */
+    int32_t field;            /* 1: the waveform starts with a 160-sample field (sets the time origin) */
+    const double *cfo;        /* device, cycles per sample per frame; NULL = 0 */
+    const double *ow2;        /* device, noise variance per complex sample per frame; NULL = no noise */
+    const int32_t *delay;     /* device, window index of waveform sample 0 per frame; NULL = 0; any sign */
+    uint64_t seed;
+    int64_t first_frame;      /* global index of frame 0, as in wce_synth_frames */
+} wce_channel_par;
+
+int wce_modulate(wce_ctx *ctx, const wce_complex *tx_pre, int64_t pre_stride, const wce_complex *sym,
+                 int64_t frame_stride, int64_t block_stride, int32_t n_blocks, int64_t n_frames,
+                 wce_complex *wave, int64_t wave_stride, void *stream);
+int wce_channel(wce_ctx *ctx, const wce_complex *wave, int64_t wave_stride, int64_t wave_len, int64_t n_frames,
+                const wce_channel_par *p, wce_complex *capture, int64_t capture_stride, int64_t capture_len,
+                void *stream);
+int wce_transmit(wce_ctx *ctx, const wce_complex *tx_pre, int64_t pre_stride, const wce_complex *sym,
+                 int64_t frame_stride, int64_t block_stride, int32_t n_blocks, int64_t n_frames,
+                 const wce_channel_par *p, wce_complex *capture, int64_t capture_stride, int64_t capture_len,
+                 void *stream);
 
 /* Non-finite guard.  The reference passes NaN/Inf through
  * silently: main.c's PS_MMSE returns NaN x 53 (main.c:148-212), a zero pilot
