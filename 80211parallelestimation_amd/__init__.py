@@ -12,6 +12,7 @@ from .wce import (  # noqa: F401
     DEMOD_REF_TX, DEMOD_TRACK, MOD_BPSK, MOD_QAM16, MOD_QAM64, MOD_QPSK, Demod, DemodOut,
     DEC_TERMINATED, RATE_1_2, RATE_2_3, RATE_3_4, info_bits, ReencodePar, ReencodeOut,
     ChannelPar, pdp_taps,
+    TRACK_KNOWN_TX, TRACK_PHASE, TRACK_REF_TX, Track, TrackOut,
 )
 
 __version__ = "0.1.0"

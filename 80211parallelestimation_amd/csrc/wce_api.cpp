@@ -1073,6 +1073,85 @@ int wce_demodulate(wce_ctx *c, const wce_frames *in, const wce_demod *p, const w
     return rc ? fail(rc, "demod launch") : WCE_OK;
 }
 
+// the doubles nearest to 1 / sqrt(1, 2, 10, 42), as wce_demodulate; 0 for an unknown modulation
+static double mod_K(int32_t modulation)
+{
+    switch (modulation) {
+    case WCE_MOD_BPSK: return 1.0;
+    case WCE_MOD_QPSK: return 0.70710678118654752440;
+    case WCE_MOD_QAM16: return 0.31622776601683793320;
+    case WCE_MOD_QAM64: return 0.15430334996209191026;
+    default: return 0.0;
+    }
+}
+
+// ---------------------------------------------------------------- per-block tracking
+int wce_track_demodulate(wce_ctx *c, const wce_frames *in, const wce_track *p, const wce_track_out *out, void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    if (!in || !p || !out) return fail(WCE_EINVAL, "wce_track_demodulate: null frames, parameters or outputs");
+    if (!in->tx || !in->rx) return fail(WCE_EINVAL, "wce_track_demodulate: tx/rx required");
+    if (!p->h) return fail(WCE_EINVAL, "wce_track_demodulate: h required");
+    if (!out->eq && !out->sym && !out->theta && !out->evm && !out->nerr && !out->h_blocks && !out->h_last)
+        return fail(WCE_EINVAL, "wce_track_demodulate: no output requested");
+    if (p->h_stride < wce::NSC) return fail(WCE_EINVAL, "wce_track_demodulate: h_stride < 53");
+    const double K = mod_K(p->modulation);
+    if (K == 0.0) return fail(WCE_EINVAL, "wce_track_demodulate: unknown modulation");
+    if (p->flags & ~(WCE_TRACK_PHASE | WCE_TRACK_REF_TX | WCE_TRACK_KNOWN_TX))
+        return fail(WCE_EINVAL, "wce_track_demodulate: unknown flag bits");
+    if (!(p->scale > 0.0) || p->scale * 0.0 != 0.0)
+        return fail(WCE_EINVAL, "wce_track_demodulate: scale not positive and finite");
+    if (!(p->mu >= 0.0 && p->mu <= 1.0)) return fail(WCE_EINVAL, "wce_track_demodulate: mu outside [0, 1]");
+    if (p->beta < 0 || p->beta > 4) return fail(WCE_EINVAL, "wce_track_demodulate: beta outside 0..4");
+    // the frames: the fields the call reads (block, semantics and the preambles are ignored)
+    wce_frames fr = *in;
+    fr.rx_pre = fr.tx_pre = nullptr;
+    fr.block = 0;
+    fr.semantics = WCE_SEM_C;
+    int rc = check_frames(&fr, true);
+    if (rc) return rc;
+    const int64_t n = in->n_frames;
+    const int64_t span = (wce::NBLK - 1);
+    if (out->eq && (out->eq_block_stride < wce::NSC ||
+                    (n > 1 && out->eq_frame_stride < span * out->eq_block_stride + wce::NSC)))
+        return fail(WCE_EINVAL, "wce_track_demodulate: eq strides too small");
+    if (out->sym && (out->sym_block_stride < wce::NSC ||
+                     (n > 1 && out->sym_frame_stride < span * out->sym_block_stride + wce::NSC)))
+        return fail(WCE_EINVAL, "wce_track_demodulate: sym strides too small");
+    if (out->h_blocks && (out->hb_block_stride < wce::NSC ||
+                          (n > 1 && out->hb_frame_stride < span * out->hb_block_stride + wce::NSC)))
+        return fail(WCE_EINVAL, "wce_track_demodulate: h_blocks strides too small");
+    if (out->h_last && out->h_last_stride < wce::NSC) return fail(WCE_EINVAL, "wce_track_demodulate: h_last_stride < 53");
+    if (reinterpret_cast<uintptr_t>(out->theta) % 8 || reinterpret_cast<uintptr_t>(out->evm) % 8)
+        return fail(WCE_EINVAL, "wce_track_demodulate: theta or evm not 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out->nerr) % 4)
+        return fail(WCE_EINVAL, "wce_track_demodulate: nerr not 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(p->h) % 16 || reinterpret_cast<uintptr_t>(out->eq) % 16)
+        return fail(WCE_EINVAL, "wce_track_demodulate: h or eq not 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out->h_blocks) % 16 || reinterpret_cast<uintptr_t>(out->h_last) % 16)
+        return fail(WCE_EINVAL, "wce_track_demodulate: h_blocks or h_last not 16-byte aligned");
+    if (n == 0) return WCE_OK;
+    wce::TrackArgs a{};
+    a.tx = reinterpret_cast<const double *>(in->tx);
+    a.rx = reinterpret_cast<const double *>(in->rx);
+    a.h = reinterpret_cast<const double *>(p->h);
+    a.fs = in->frame_stride; a.bs = in->block_stride; a.hs = p->h_stride; a.n = n;
+    a.mod = p->modulation; a.flags = p->flags;
+    a.scale = p->scale; a.d = p->scale * K;
+    a.mu = p->mu; a.beta = p->beta;
+    a.eq = reinterpret_cast<double *>(out->eq);
+    a.sym = out->sym; a.theta = out->theta; a.evm = out->evm; a.nerr = out->nerr;
+    a.eqfs = out->eq_frame_stride; a.eqbs = out->eq_block_stride;
+    a.symfs = out->sym_frame_stride; a.symbs = out->sym_block_stride;
+    a.hb = reinterpret_cast<double *>(out->h_blocks);
+    a.hbfs = out->hb_frame_stride; a.hbbs = out->hb_block_stride;
+    a.hl = reinterpret_cast<double *>(out->h_last);
+    a.hls = out->h_last_stride;
+    DeviceGuard g(c->device);
+    rc = wce::launch_track(a, stream);
+    return rc ? fail(rc, "track launch") : WCE_OK;
+}
+
 // ---------------------------------------------------------------- decoding
 int wce_decode_info_bits(int32_t modulation, int32_t rate)
 {
@@ -1119,6 +1198,40 @@ int wce_soft_demap(wce_ctx *c, const wce_complex *eq, int64_t eq_frame_stride, i
     a.hlt = reinterpret_cast<const double *>(p->h_lt);
     a.efs = eq_frame_stride; a.ebs = eq_block_stride; a.hs = p->h_stride; a.n = n;
     a.mod = p->modulation; a.d = p->scale * K;
+    a.llr = llr; a.lfs = llr_frame_stride; a.lbs = llr_block_stride;
+    DeviceGuard g(c->device);
+    const int rc = wce::launch_demap(a, stream);
+    return rc ? fail(rc, "soft demap launch") : WCE_OK;
+}
+
+int wce_soft_demap_blocks(wce_ctx *c, const wce_complex *eq, int64_t eq_frame_stride, int64_t eq_block_stride,
+                          const wce_complex *hb, int64_t hb_frame_stride, int64_t hb_block_stride, int32_t modulation,
+                          double scale, int64_t n, float *llr, int64_t llr_frame_stride, int64_t llr_block_stride,
+                          void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    if (!eq || !hb || !llr) return fail(WCE_EINVAL, "wce_soft_demap_blocks: null eq, hb or llr");
+    const double K = mod_K(modulation);
+    if (K == 0.0) return fail(WCE_EINVAL, "wce_soft_demap_blocks: unknown modulation");
+    if (!(scale > 0.0) || scale * 0.0 != 0.0)
+        return fail(WCE_EINVAL, "wce_soft_demap_blocks: scale not positive and finite");
+    if (n < 0 || n > 0x7fffffffll) return fail(WCE_EINVAL, "wce_soft_demap_blocks: n_frames < 0 or > 2^31 - 1");
+    if (!strides_hold(n, eq_frame_stride, eq_block_stride, wce::NSC))
+        return fail(WCE_EINVAL, "wce_soft_demap_blocks: eq strides too small");
+    if (!strides_hold(n, hb_frame_stride, hb_block_stride, wce::NSC))
+        return fail(WCE_EINVAL, "wce_soft_demap_blocks: hb strides too small");
+    if (!strides_hold(n, llr_frame_stride, llr_block_stride, 48 * (int64_t)modulation))
+        return fail(WCE_EINVAL, "wce_soft_demap_blocks: llr strides too small");
+    if (reinterpret_cast<uintptr_t>(eq) % 16 || reinterpret_cast<uintptr_t>(hb) % 16)
+        return fail(WCE_EINVAL, "wce_soft_demap_blocks: eq or hb not 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(llr) % 4) return fail(WCE_EINVAL, "wce_soft_demap_blocks: llr not 4-byte aligned");
+    if (n == 0) return WCE_OK;
+    wce::DemapArgs a{};
+    a.eq = reinterpret_cast<const double *>(eq);
+    a.hb = reinterpret_cast<const double *>(hb);
+    a.hbfs = hb_frame_stride; a.hbbs = hb_block_stride;
+    a.efs = eq_frame_stride; a.ebs = eq_block_stride; a.n = n;
+    a.mod = modulation; a.d = scale * K;
     a.llr = llr; a.lfs = llr_frame_stride; a.lbs = llr_block_stride;
     DeviceGuard g(c->device);
     const int rc = wce::launch_demap(a, stream);

@@ -14,7 +14,8 @@
 // entry per level, packed into one constant per bit.  A lane's soft bits (up to
 // 6) go to their deinterleaved places of the block through LDS, so the float
 // row leaves as contiguous 256-byte stores.  HBM-bound: 12.7 KB of eq in, 2.9 to
-// 17.3 KB of soft bits out per frame.
+// 17.3 KB of soft bits out per frame.  demap_kernel<MOD, true> (wce_soft_demap_blocks)
+// reads Hu_b from a row per block, wce_track_demodulate's h_blocks, 12.7 KB more.
 //
 // Decoder.  One wave per frame, lane s' = successor state.  A step is two
 // ds_bpermute reads of the metrics of the predecessors 2 (s' & 31) and + 1, one
@@ -118,8 +119,9 @@ __device__ __forceinline__ double2 dc_blend(double2 hlt, double2 hps, int b)
     return make_double2(fma(hlt.x, wlt, hps.x * wps), fma(hlt.y, wlt, hps.y * wps));
 }
 
-// frame f on one wave; buf: this wave's two block rows of MOD * 48 floats in LDS
-template <int MOD>
+// frame f on one wave; buf: this wave's two block rows of MOD * 48 floats in LDS.  BLK: Hu_b is the row a.hb holds
+// for block b (15 more loads per lane, issued with eq's), not h or the h / h_lt blend
+template <int MOD, bool BLK>
 __device__ __forceinline__ void demap_frame(const DemapArgs &a, int64_t f, int lane, float *buf)
 {
     constexpr int NB = MOD == 1 ? 1 : MOD / 2;   // bits per axis; also the interleaver's s
@@ -128,14 +130,20 @@ __device__ __forceinline__ void demap_frame(const DemapArgs &a, int64_t f, int l
     const int k = act ? lane : 0;
     const uint32_t ko = 16u * (uint32_t)k;
     const bool data = act && k != WCE_P0 && k != WCE_P1 && k != WCE_P2 && k != WCE_P3 && k != WCE_DC;
-    const bool blend = a.hlt != nullptr;
+    const bool blend = !BLK && a.hlt != nullptr;
 
     // every load of the frame, issued before any use
-    double2 ev[NBLK];
+    double2 ev[NBLK], hv[BLK ? NBLK : 1];
 #pragma unroll
     for (int b = 0; b < NBLK; b++) ev[b] = dc_ld_nt(a.eq, f * a.efs + b * a.ebs, ko);
-    const double2 hps = dc_ld(a.h, f * a.hs, ko);
-    const double2 hlt = blend ? dc_ld(a.hlt, f * a.hs, ko) : make_double2(0, 0);
+    double2 hps = make_double2(0, 0), hlt = make_double2(0, 0);
+    if constexpr (BLK) {
+#pragma unroll
+        for (int b = 0; b < NBLK; b++) hv[b] = dc_ld_nt(a.hb, f * a.hbfs + b * a.hbbs, ko);
+    } else {
+        hps = dc_ld(a.h, f * a.hs, ko);
+        if (blend) hlt = dc_ld(a.hlt, f * a.hs, ko);
+    }
 
     // where this lane's bits go: transmitted bit j = MOD * (index among the data subcarriers) + m is coded bit
     // 16 i - (NCB - 1) floor(16 i / NCB), i = s floor(j / s) + (j + floor(16 j / NCB)) mod s  (17.3.5.7's inverse)
@@ -151,7 +159,7 @@ __device__ __forceinline__ void demap_frame(const DemapArgs &a, int64_t f, int l
 
 #pragma unroll
     for (int b = 0; b < NBLK; b++) {
-        const double2 hu = blend ? dc_blend(hlt, hps, b) : hps;
+        const double2 hu = BLK ? hv[BLK ? b : 0] : blend ? dc_blend(hlt, hps, b) : hps;
         const double w = hu.x * hu.x + hu.y * hu.y;
         const bool ok = isfinite(ev[b].x) && isfinite(ev[b].y) && isfinite(hu.x) && isfinite(hu.y);
         float L[MOD];
@@ -172,7 +180,7 @@ __device__ __forceinline__ void demap_frame(const DemapArgs &a, int64_t f, int l
     wave_lds_sync();
 }
 
-template <int MOD>
+template <int MOD, bool BLK>
 __global__ __launch_bounds__(64 * DC_WAVES) void demap_kernel(DemapArgs a)
 {
     __shared__ float rows[DC_WAVES][2 * NDATA * MOD];
@@ -180,7 +188,14 @@ __global__ __launch_bounds__(64 * DC_WAVES) void demap_kernel(DemapArgs a)
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 #pragma unroll 1
     for (int64_t f = (int64_t)blockIdx.x * DC_WAVES + wv; f < a.n; f += (int64_t)gridDim.x * DC_WAVES)
-        demap_frame<MOD>(a, f, lane, rows[wv]);
+        demap_frame<MOD, BLK>(a, f, lane, rows[wv]);
+}
+
+template <int MOD>
+static void demap_launch(const DemapArgs &a, dim3 g, dim3 t, hipStream_t s)
+{
+    if (a.hb) hipLaunchKernelGGL((demap_kernel<MOD, true>), g, t, 0, s, a);
+    else hipLaunchKernelGGL((demap_kernel<MOD, false>), g, t, 0, s, a);
 }
 
 int launch_demap(const DemapArgs &a, void *stream)
@@ -192,10 +207,10 @@ int launch_demap(const DemapArgs &a, void *stream)
     if (blocks > DC_GRID_CAP) blocks = DC_GRID_CAP;
     const dim3 g((uint32_t)blocks), t(64 * DC_WAVES);
     switch (a.mod) {
-    case WCE_MOD_BPSK: hipLaunchKernelGGL(demap_kernel<1>, g, t, 0, s, a); break;
-    case WCE_MOD_QPSK: hipLaunchKernelGGL(demap_kernel<2>, g, t, 0, s, a); break;
-    case WCE_MOD_QAM16: hipLaunchKernelGGL(demap_kernel<4>, g, t, 0, s, a); break;
-    case WCE_MOD_QAM64: hipLaunchKernelGGL(demap_kernel<6>, g, t, 0, s, a); break;
+    case WCE_MOD_BPSK: demap_launch<1>(a, g, t, s); break;
+    case WCE_MOD_QPSK: demap_launch<2>(a, g, t, s); break;
+    case WCE_MOD_QAM16: demap_launch<4>(a, g, t, s); break;
+    case WCE_MOD_QAM64: demap_launch<6>(a, g, t, s); break;
     default: return WCE_EINVAL;
     }
     return hipGetLastError() == hipSuccess ? WCE_OK : WCE_EHIP;

@@ -227,6 +227,48 @@ __device__ __forceinline__ double2 row_bcast_n(double2 v, int n)   // n a consta
     }
 }
 
+// ---------------------------------------------------------------- demodulation (wce_demod.hip, wce_track.hip)
+// the slicer of lane k: the data lanes' modulation, BPSK on the pilot lanes
+struct DmLane {
+    double d, inv2d, half, top;   // level spacing / 2, 1 / (2 d), M / 2, M - 1
+    int m1, shift;                // M - 1; bits per axis (0: the real axis only)
+};
+__device__ __forceinline__ int dm_level(double v, const DmLane &c)
+{
+    const double t = floor(v * c.inv2d + c.half);
+    return (int)fmin(fmax(t, 0.0), c.top);   // a NaN goes to level 0; its label is 0xFF anyway
+}
+// label of point e (0xFF where e is not finite) and the decided point
+__device__ __forceinline__ uint32_t dm_slice(double2 e, const DmLane &c, double2 &dec)
+{
+    const int ii = dm_level(e.x, c), iq = c.shift ? dm_level(e.y, c) : 0;
+    dec = make_double2((double)(2 * ii - c.m1) * c.d, c.shift ? (double)(2 * iq - c.m1) * c.d : 0.0);
+    const uint32_t s = c.shift ? (uint32_t)(ii ^ (ii >> 1)) << c.shift | (uint32_t)(iq ^ (iq >> 1)) : (uint32_t)ii;
+    return isfinite(e.x) && isfinite(e.y) ? s : 0xFFu;
+}
+
+// element (uniform index u) + (this lane's byte offset ko) of a complex array: the uniform part stays in scalar
+// registers and the lane's part is one 32-bit offset, so a frame's 45 addresses cost no vector registers
+__device__ __forceinline__ const v2d *dm_at(const double *p, int64_t u, uint32_t ko)
+{
+    return reinterpret_cast<const v2d *>(reinterpret_cast<const char *>(p + 2 * u) + ko);
+}
+__device__ __forceinline__ double2 dm_ld(const double *p, int64_t u, uint32_t ko)
+{
+    const v2d t = *dm_at(p, u, ko);
+    return make_double2(t[0], t[1]);
+}
+__device__ __forceinline__ double2 dm_ld_nt(const double *p, int64_t u, uint32_t ko)
+{
+    const v2d t = __builtin_nontemporal_load(dm_at(p, u, ko));
+    return make_double2(t[0], t[1]);
+}
+__device__ __forceinline__ void dm_st_nt(double *p, int64_t u, uint32_t ko, double2 v)
+{
+    v2d t = {v.x, v.y};
+    __builtin_nontemporal_store(t, const_cast<v2d *>(dm_at(p, u, ko)));
+}
+
 // ---------------------------------------------------------------- DPP64 FMAs (quad kernels)
 // acc -= l conj(R[lane N of the 16-lane row]): gfx950's DPP64 row_newbcast on
 // v_fmac_f64 hands the broadcast operand straight to the FMA (4 VALU instead

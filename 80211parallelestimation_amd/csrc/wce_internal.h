@@ -238,10 +238,33 @@ struct DemodArgs {
     int64_t eqfs, eqbs, symfs, symbs;
 };
 
+// per-block tracker (wce_track.hip): frames as LsArgs; h rows of stride hs are H_0
+struct TrackArgs {
+    const double *tx, *rx, *h;
+    int64_t fs, bs, hs, n;
+    int32_t mod;          // WCE_MOD_*: bits per data symbol
+    uint32_t flags;       // WCE_TRACK_*
+    double scale, d;      // pilot and data level half-spacing: scale, scale K
+    double mu;            // time weight, 0 .. 1 (0: no update)
+    int32_t beta;         // frequency half-window, 0 .. 4
+    double *eq;           // each output may be null
+    uint8_t *sym;
+    double *theta, *evm;
+    uint32_t *nerr;
+    int64_t eqfs, eqbs, symfs, symbs;
+    double *hb;           // hb[f*hbfs + b*hbbs + k] = H_b
+    int64_t hbfs, hbbs;
+    double *hl;           // hl[f*hls + k] = H_15
+    int64_t hls;
+};
+
 // soft demapper (wce_decode.hip): eq[f*efs + b*ebs + k], h / hlt rows of stride hs (hlt null: no blend),
-// llr[f*lfs + b*lbs + (0..48 mod - 1)] in deinterleaved coded order
+// llr[f*lfs + b*lbs + (0..48 mod - 1)] in deinterleaved coded order.  hb set (wce_soft_demap_blocks): h and hlt are
+// not read and Hu_b[k] = hb[f*hbfs + b*hbbs + k]
 struct DemapArgs {
     const double *eq, *h, *hlt;
+    const double *hb;
+    int64_t hbfs, hbbs;
     int64_t efs, ebs, hs, n;
     int32_t mod;          // WCE_MOD_*: bits per data symbol
     double d;             // level half-spacing scale K
@@ -300,6 +323,7 @@ int launch_transmit(const TxArgs &a, void *stream);
 int launch_ls(const State *st, const LsArgs &a, void *stream);
 int launch_demod(const DemodArgs &a, void *stream);
 int launch_demap(const DemapArgs &a, void *stream);
+int launch_track(const TrackArgs &a, void *stream);
 int launch_reencode(const ReencodeArgs &a, void *stream);
 // WCE_EINVAL where the survivor memory of T steps does not fit a workgroup's LDS
 int launch_viterbi(const ViterbiArgs &a, void *stream);

@@ -45,6 +45,9 @@ SEM_MATLAB = 1     # WiFi_channel_estimation_*.m semantics
 MOD_BPSK, MOD_QPSK, MOD_QAM16, MOD_QAM64 = 1, 2, 4, 6   # wce_demod.modulation: bits per data symbol
 DEMOD_TRACK = 1 << 0     # remove each block's common pilot phase
 DEMOD_REF_TX = 1 << 1    # EVM against tx instead of the decided point
+TRACK_PHASE = 1 << 0     # WCE_TRACK_PHASE: per-block common pilot phase, as DEMOD_TRACK
+TRACK_REF_TX = 1 << 1    # WCE_TRACK_REF_TX: EVM against tx, as DEMOD_REF_TX
+TRACK_KNOWN_TX = 1 << 2  # WCE_TRACK_KNOWN_TX: the data-aided bound, nothing decided is fed back
 RATE_1_2, RATE_2_3, RATE_3_4 = 0, 1, 2   # WCE_RATE_*: code rate of wce_viterbi_decode
 DEC_TERMINATED = 1 << 0  # WCE_DEC_TERMINATED: trace back from state 0
 
@@ -98,6 +101,20 @@ class DemodOut(ctypes.Structure):
     _fields_ = [("eq", c_void_p), ("sym", c_void_p), ("theta", c_void_p), ("evm", c_void_p), ("nerr", c_void_p),
                 ("eq_frame_stride", c_int64), ("eq_block_stride", c_int64), ("sym_frame_stride", c_int64),
                 ("sym_block_stride", c_int64)]
+
+
+class Track(ctypes.Structure):
+    """struct wce_track (include/wce.h)."""
+    _fields_ = [("h", c_void_p), ("h_stride", c_int64), ("modulation", c_int32), ("flags", c_uint32),
+                ("scale", c_double), ("mu", c_double), ("beta", c_int32)]
+
+
+class TrackOut(ctypes.Structure):
+    """struct wce_track_out (include/wce.h)."""
+    _fields_ = [("eq", c_void_p), ("sym", c_void_p), ("theta", c_void_p), ("evm", c_void_p), ("nerr", c_void_p),
+                ("eq_frame_stride", c_int64), ("eq_block_stride", c_int64), ("sym_frame_stride", c_int64),
+                ("sym_block_stride", c_int64), ("h_blocks", c_void_p), ("hb_frame_stride", c_int64),
+                ("hb_block_stride", c_int64), ("h_last", c_void_p), ("h_last_stride", c_int64)]
 
 
 class ReencodePar(ctypes.Structure):
@@ -178,6 +195,9 @@ ABI = {
     "wce_front_end_blocks_at": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64,
                                 c_void_p, c_int64, c_int64, c_void_p],
     "wce_demodulate": [c_void_p, POINTER(Frames), POINTER(Demod), POINTER(DemodOut), c_void_p],
+    "wce_track_demodulate": [c_void_p, POINTER(Frames), POINTER(Track), POINTER(TrackOut), c_void_p],
+    "wce_soft_demap_blocks": [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_double,
+                              c_int64, c_void_p, c_int64, c_int64, c_void_p],
     "wce_soft_demap": [c_void_p, c_void_p, c_int64, c_int64, POINTER(Demod), c_int64, c_void_p, c_int64, c_int64,
                        c_void_p],
     "wce_viterbi_decode": [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_uint32, c_int64, c_void_p,
@@ -549,6 +569,89 @@ class Context:
         synchronize()
         return {n: a.numpy() for n, a in d.items()}
 
+    def track_demodulate(self, frames: Frames, h, mu, beta, h_stride=NSC, modulation=MOD_BPSK, scale=8.8753,
+                         phase=True, ref_tx=True, known_tx=False, eq=None, sym=None, theta=None, evm=None, nerr=None,
+                         h_blocks=None, h_last=None, stream=None, eq_frame_stride=None, eq_block_stride=NSC,
+                         sym_frame_stride=None, sym_block_stride=NSC, hb_frame_stride=None, hb_block_stride=NSC,
+                         h_last_stride=NSC):
+        """wce_track_demodulate on device arrays: demodulate `frames` block by block, starting each frame from the
+        estimate h [n][h_stride] and re-estimating the channel after every block from the decided symbols (the
+        tx symbols with known_tx: the data-aided bound), averaged over the 2 beta + 1 neighbouring subcarriers
+        (beta 0..4) and moved towards that by the time weight mu (0..1; 0: h throughout).  phase, ref_tx: as
+        demodulate's track and ref_tx.  Outputs, each optional: demodulate's eq, sym, theta, evm and nerr; h_blocks
+        complex [n][15][hb_block_stride], the estimate each block was equalized with (soft_demap_blocks reads
+        it); h_last complex [n][h_last_stride], the estimate after the last block.  Frame strides default to 15
+        block strides."""
+        p = Track(_addr(h), h_stride, modulation, (TRACK_PHASE if phase else 0) | (TRACK_REF_TX if ref_tx else 0) |
+                  (TRACK_KNOWN_TX if known_tx else 0), scale, mu, beta)
+        o = TrackOut(_addr(eq), _addr(sym), _addr(theta), _addr(evm), _addr(nerr),
+                     eq_frame_stride if eq_frame_stride is not None else NBLK * eq_block_stride, eq_block_stride,
+                     sym_frame_stride if sym_frame_stride is not None else NBLK * sym_block_stride, sym_block_stride,
+                     _addr(h_blocks), hb_frame_stride if hb_frame_stride is not None else NBLK * hb_block_stride,
+                     hb_block_stride, _addr(h_last), h_last_stride)
+        _check(_lib.wce_track_demodulate(self.handle, byref(frames), byref(p), byref(o), stream),
+               "wce_track_demodulate")
+
+    def _track_device(self, fr, B, dh, mu, beta, modulation, scale, phase, ref_tx, known_tx=False):
+        """queue track_demodulate with every output; -> name -> DeviceArray (read them after a synchronize)"""
+        d = {"eq": DeviceArray((B, NBLK, NSC), zero=True), "sym": DeviceArray((B, NBLK, NSC), np.uint8, zero=True),
+             "theta": DeviceArray((B, NBLK), np.float64, zero=True), "evm": DeviceArray((B,), np.float64, zero=True),
+             "nerr": DeviceArray((B,), np.uint32, zero=True), "h_blocks": DeviceArray((B, NBLK, NSC), zero=True),
+             "h_last": DeviceArray((B, NSC), zero=True)}
+        self.track_demodulate(fr, dh, mu, beta, NSC, modulation, scale, phase, ref_tx, known_tx, **d)
+        return d
+
+    def _track_inputs(self, tx, rx, h):
+        """host frames [B][15][53] and estimates [B][53], checked, on the device -> (B, frames, keep)"""
+        tx, rx, h = _as_c128(tx), _as_c128(rx), _as_c128(h)
+        B = tx.shape[0]
+        if tx.shape != (B, NBLK, NSC) or rx.shape != tx.shape:
+            raise ValueError("tx/rx must be [B][15][53] complex")
+        if h.shape != (B, NSC):
+            raise ValueError("h must be [B][53] complex")
+        keep = [DeviceArray.from_numpy(tx), DeviceArray.from_numpy(rx), DeviceArray.from_numpy(h)]
+        return B, self.frames(keep[0], keep[1], B), keep
+
+    def track_demodulate_host(self, tx, rx, h, mu=0.5, beta=2, modulation=MOD_BPSK, scale=8.8753, phase=True,
+                              ref_tx=True, known_tx=False):
+        """Convenience: host frames [B][15][53] and starting estimates h [B][53] -> dict of host arrays eq, sym,
+        theta, evm, nerr (as demodulate_host), h_blocks [B][15][53] and h_last [B][53]."""
+        B, fr, keep = self._track_inputs(tx, rx, h)
+        d = self._track_device(fr, B, keep[2], mu, beta, modulation, scale, phase, ref_tx, known_tx)
+        synchronize()
+        return {n: a.numpy() for n, a in d.items()}
+
+    def track_decode_host(self, tx, rx, h, modulation=MOD_BPSK, rate=RATE_1_2, mu=0.5, beta=2, scale=8.8753,
+                          phase=True, terminated=True, ref_bits=None):
+        """Convenience: the tracked receive chain on host frames [B][15][53] and starting estimates h [B][53]:
+        track_demodulate, soft_demap_blocks on its eq and h_blocks, viterbi_decode at `rate`, queued on one stream
+        with no host hop between them -> dict of host arrays: "demod" (the dict of track_demodulate_host), llr
+        float32 [B][15][48 * modulation], bits uint8 [B][T] and, with ref_bits [B][T], nbiterr uint32 [B]."""
+        B, fr, keep = self._track_inputs(tx, rx, h)
+        trk = self._track_device(fr, B, keep[2], mu, beta, modulation, scale, phase, True)
+        d = self._decode_device(trk["eq"], None, None, B, modulation, rate, scale, terminated, ref_bits,
+                                h_blocks=trk["h_blocks"])
+        synchronize()
+        res = self._decode_result(d, modulation, rate)
+        res["demod"] = {n: a.numpy() for n, a in trk.items()}
+        return res
+
+    def soft_demap_blocks(self, eq, h_blocks, n_frames, modulation=MOD_BPSK, scale=8.8753, llr=None,
+                          eq_frame_stride=None, eq_block_stride=NSC, hb_frame_stride=None, hb_block_stride=NSC,
+                          llr_frame_stride=None, llr_block_stride=None, stream=None):
+        """wce_soft_demap_blocks on device arrays: soft_demap with an estimate per block, h_blocks complex
+        [n][15][hb_block_stride] (track_demodulate's): block b's soft bits are weighed by |h_blocks[b]|^2.  Where
+        every block row of a frame is the same h the soft bits are soft_demap's with that h and no h_lt, bit for
+        bit.  Strides as soft_demap."""
+        lbs = llr_block_stride if llr_block_stride is not None else 48 * modulation
+        _check(_lib.wce_soft_demap_blocks(self.handle, _addr(eq),
+                                          eq_frame_stride if eq_frame_stride is not None else NBLK * eq_block_stride,
+                                          eq_block_stride, _addr(h_blocks),
+                                          hb_frame_stride if hb_frame_stride is not None else NBLK * hb_block_stride,
+                                          hb_block_stride, modulation, scale, n_frames, _addr(llr),
+                                          llr_frame_stride if llr_frame_stride is not None else NBLK * lbs, lbs,
+                                          stream), "wce_soft_demap_blocks")
+
     def soft_demap(self, eq, h, n_frames, h_lt=None, h_stride=NSC, modulation=MOD_BPSK, scale=8.8753, llr=None,
                    eq_frame_stride=None, eq_block_stride=NSC, llr_frame_stride=None, llr_block_stride=None,
                    stream=None):
@@ -804,8 +907,9 @@ class Context:
         dd["bits"] = np.unpackbits(dd["bits"], axis=1, bitorder="little")[:, :info_bits(modulation, rate)]
         return d["h_dd"].numpy(), dd
 
-    def _decode_device(self, deq, dh, dhlt, B, modulation, rate, scale, terminated, ref_bits):
-        """queue soft_demap and viterbi_decode on dense device arrays (eq [B][15][53], h and h_lt [B][53]);
+    def _decode_device(self, deq, dh, dhlt, B, modulation, rate, scale, terminated, ref_bits, h_blocks=None):
+        """queue soft_demap and viterbi_decode on dense device arrays (eq [B][15][53], h and h_lt [B][53]; or, with
+        h_blocks [B][15][53], soft_demap_blocks and neither h nor h_lt);
         -> name -> DeviceArray (read them after a synchronize, through _decode_result)"""
         T = info_bits(modulation, rate)
         d = {"llr": DeviceArray((B, NBLK, 48 * modulation), np.float32, zero=True),
@@ -817,7 +921,10 @@ class Context:
                 raise ValueError("ref_bits must be [B][T] with T = info_bits(modulation, rate)")
             dref = DeviceArray.from_numpy(np.packbits(ref, axis=1, bitorder="little"))
             d["nbiterr"] = DeviceArray((B,), np.uint32, zero=True)
-        self.soft_demap(deq, dh, B, dhlt, NSC, modulation, scale, d["llr"])
+        if h_blocks is not None:
+            self.soft_demap_blocks(deq, h_blocks, B, modulation, scale, d["llr"])
+        else:
+            self.soft_demap(deq, dh, B, dhlt, NSC, modulation, scale, d["llr"])
         self.viterbi_decode(d["llr"], B, modulation, rate, terminated, d["bits"], ref_bits=dref,
                             nbiterr=d.get("nbiterr"))
         d["_ref"] = dref   # read by the queued decoder until the caller synchronises
@@ -993,14 +1100,16 @@ class Context:
         return self._estimate_device(dtx, drx, dpre, B, mask, block, eq_source, semantics, dtp, ls_f32, dow2)
 
     def _estimate_device(self, dtx, drx, dpre, B, mask, block, eq_source, semantics, dtp, ls_f32, dow2, demod=None,
-                         decode=None, dd_iterations=0):
+                         decode=None, dd_iterations=0, tracker=None):
         """estimate_host's device half: dense [B][15][53] frames (and rx_pre [B][53], tx_pre [53], ow2 [B] or
         None) on the device -> dict of host outputs.  demod: (source bit, modulation, scale, track) queues
         demodulate behind the estimate with h = that estimator's output and h_lt = lt_ls; the dict gains "demod".
         decode (needs demod): (rate, ref_bits, terminated) queues soft_demap and viterbi_decode behind that, on
         the demodulated eq where it lies on the device; the dict gains "decode".  dd_iterations n > 0 (needs
         decode): n decision-directed rounds (_dd_device) behind that, on the decoder's bits and the demodulator's
-        block phases; the dict gains "h_dd" and "decode_dd"."""
+        block phases; the dict gains "h_dd" and "decode_dd".  tracker (needs demod): (mu, beta): track_demodulate takes
+        demodulate's place with h = the source's output and no h_lt, and soft_demap_blocks soft_demap's; "demod"
+        gains h_blocks and h_last."""
         names = [("lt_ls", LT_LS), ("ps_linear", PS_LINEAR), ("ps_cubic", PS_CUBIC), ("ps_sinc", PS_SINC),
                  ("ps_mmse", PS_MMSE)]
         lsdt = np.complex64 if ls_f32 else np.complex128
@@ -1015,10 +1124,13 @@ class Context:
         dem = dec = dd = None
         if demod is not None:   # same (null) stream: it reads the estimate's outputs in order, no host hop
             src = {bit: n for n, bit in names}[demod[0]]
-            dem = self._demod_device(fr, B, outs[src], outs["lt_ls"], demod[1], demod[2], demod[3], True)
+            if tracker is not None:
+                dem = self._track_device(fr, B, outs[src], tracker[0], tracker[1], demod[1], demod[2], demod[3], True)
+            else:
+                dem = self._demod_device(fr, B, outs[src], outs["lt_ls"], demod[1], demod[2], demod[3], True)
             if decode is not None:
                 dec = self._decode_device(dem["eq"], outs[src], outs["lt_ls"], B, demod[1], decode[0], demod[2],
-                                          decode[2], decode[1])
+                                          decode[2], decode[1], h_blocks=dem.get("h_blocks"))
                 if dd_iterations:
                     dd = self._dd_device(fr, B, dec["bits"], dem["theta"], demod[1], decode[0], demod[2], decode[2],
                                          dec["_ref"], int(dd_iterations))
@@ -1057,7 +1169,7 @@ class Context:
 
     def receive_host(self, tx_packets, tx_lptot, rx_packets, rx_lptot, mask=ALL, semantics=SEM_MATLAB, cfo=False,
                      sample_offset=0, demod_source=None, modulation=MOD_BPSK, scale=8.8753, track=True,
-                     decode_rate=None, ref_bits=None, terminated=True):
+                     tracker=None, decode_rate=None, ref_bits=None, terminated=True):
         """WiFi_RX.m:17-60 for a batch, on the device with no host hop in between: host time-domain packets
         [B][>= 1200] and long training fields [B][L] of both sides -> the front end (symbols, preamble FFTs and
         each packet's sigma^2) -> estimate with each frame's own rx preamble (WCE_MMSE_FRAME_COV) and own
@@ -1075,9 +1187,18 @@ class Context:
         decode_rate: a RATE_* value (demod_source must be set): the demodulated eq stays on the device and is
         demapped and decoded there (soft_demap with the same h and h_lt, viterbi_decode at that rate, `terminated`),
         queued behind the demodulation; the dict gains "decode", the dict of decode_host (nbiterr with ref_bits
-        [B][T]).  A frame of NaN symbols decodes from all-zero soft bits to all-zero bits."""
+        [B][T]).  A frame of NaN symbols decodes from all-zero soft bits to all-zero bits.
+        tracker: (mu, beta) (demod_source must be set): the channel is tracked through the packet --
+        track_demodulate takes demodulate's place, starting from h = that estimator's output with no h_lt blend
+        (`track` is its phase flag), and with a decode_rate soft_demap_blocks takes soft_demap's with the estimate
+        of each block; "demod" gains h_blocks and h_last.  None: the calls and bits above."""
+        if tracker is not None:
+            if demod_source is None or len(tracker) != 2:
+                raise ValueError("tracker is (mu, beta) and needs demod_source")
+            tracker = (float(tracker[0]), int(tracker[1]))
         return self._receive_host(tx_packets, tx_lptot, rx_packets, rx_lptot, mask, semantics, cfo, sample_offset,
-                                  demod_source, modulation, scale, track, decode_rate, ref_bits, terminated, 0)
+                                  demod_source, modulation, scale, track, decode_rate, ref_bits, terminated, 0,
+                                  tracker)
 
     def receive_iterated_host(self, tx_packets, tx_lptot, rx_packets, rx_lptot, demod_source, decode_rate,
                               dd_iterations=1, **receive):
@@ -1102,7 +1223,8 @@ class Context:
                                   decode_rate, kw["ref_bits"], kw["terminated"], int(dd_iterations))
 
     def _receive_host(self, tx_packets, tx_lptot, rx_packets, rx_lptot, mask, semantics, cfo, sample_offset,
-                      demod_source, modulation, scale, track, decode_rate, ref_bits, terminated, dd_iterations):
+                      demod_source, modulation, scale, track, decode_rate, ref_bits, terminated, dd_iterations,
+                      tracker=None):
         """receive_host's body; dd_iterations: the decision-directed rounds of receive_iterated_host"""
         dem = self._demod_request(demod_source, mask, modulation, scale, track)
         dcd = self._decode_request(decode_rate, dem, ref_bits, terminated)
@@ -1131,7 +1253,7 @@ class Context:
             pre.append(dpre)
         # same (null) stream throughout: the estimate reads the front end's outputs in order
         res = self._estimate_device(sym[0], sym[1], pre[1], B, mask | FRAME_COV, 0, PS_LINEAR, semantics, pre[0],
-                                    False, dow2, dem, dcd, dd_iterations)
+                                    False, dow2, dem, dcd, dd_iterations, tracker)
         res["ow2"] = dow2.numpy()
         if cfo:
             res["cfo"] = dcfo.numpy()

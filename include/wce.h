@@ -483,6 +483,75 @@ typedef struct {              /* every pointer device, each may be NULL = not wa
 
 int wce_demodulate(wce_ctx *ctx, const wce_frames *in, const wce_demod *p, const wce_demod_out *out, void *stream);
 
+/* ---- per-block decision-directed tracking ("spectral temporal averaging", Fernandez
+ * et al., IEEE Trans. Veh. Technol., 2012; the reference assumes the channel of a frame
+ * does not move over its 15 blocks) ----
+ * wce_track_demodulate is wce_demodulate for a channel that moves inside the frame
+ * (the reference samples at 10 MHz, 802.11p's numerology: a vehicular channel
+ * decorrelates noticeably within the 120 us of a frame).  Frame f starts from
+ * H_0 = h[f*h_stride + k], any estimate (LT_LS, PS_MMSE, wce_reencode's H_dd ...),
+ * and re-estimates the channel block by block from its own decisions, smoothed over
+ * frequency and time.  It reads in->tx, in->rx, the strides and n_frames as
+ * wce_demodulate does.  V = {0..52} without 26, pilots P = {5, 19, 33, 47}; for
+ * b = 0..14 in order:
+ *   phase     z_b, theta_b and r_b are wce_demodulate's with Hu_b = H_b (WCE_TRACK_PHASE;
+ *             z_b = 0: r_b = 1, theta_b = 0; without the flag r_b = 1, theta_b = 0).  The
+ *             rotor is conj(z_b) / sqrt(|z_b|^2) with |z_b|^2 formed in fp64: |z_b| outside
+ *             about 1e-150 .. 1e150 is outside the call's range.
+ *   equalize  e_b[k] = (rx_b[k] / H_b[k]) r_b, e_b[26] = 0.
+ *   decide    wce_demodulate's slicer: the same d, labels, 0xFF rule and BPSK pilots with
+ *             d = scale; it gives sym and the decided point dec_b[k].
+ *   known     x^_b[k] = in->tx on the pilots always, and on every k with WCE_TRACK_KNOWN_TX
+ *             (the data-aided bound: nothing decided is fed back); else x^_b[k] = dec_b[k].
+ *   estimate  G_b[k] = rx_b[k] r_b / x^_b[k], k in V.
+ *   frequency S_b[k] = the sum of G_b[j] over N_k = {j in V : |j - k| <= beta}, divided by
+ *             |N_k|.  The window is in index space: it runs across DC and is clipped at 0
+ *             and 52.  The order of the sum is the implementation's.
+ *   time      H_{b+1}[k] = H_b[k] + mu (S_b[k] - H_b[k]), k in V.  mu == 0 skips the update:
+ *             every H_b is h, bit for bit.  Entry 26 is carried from h unchanged.
+ *   score     evm and nerr as wce_demodulate (WCE_TRACK_REF_TX: EVM against in->tx).
+ * h_blocks[f][b] = H_b, the estimate block b was equalized with (wce_soft_demap_blocks
+ * weighs the soft bits by it); h_last[f] = H_15.
+ *
+ *  - Asynchronous on `stream`; nothing is read back and nothing allocated; the ctx only
+ *    selects the device.  Absent outputs cost no stores.
+ *  - A frame's bits depend only on its own data and the call's arguments.  A non-finite
+ *    rx or h entry may make later blocks of that frame non-finite within beta of it (a
+ *    non-finite pilot: the whole block and what follows); its data symbols get 0xFF and
+ *    the frame gets evm = NaN.  No other frame changes by a bit.
+ *  - WCE_EINVAL (text in wce_last_error()) before any launch: everything wce_demodulate
+ *    rejects; mu outside [0, 1] or not finite; beta outside 0..4; an unknown flag bit;
+ *    h_blocks strides too small (the rule of eq); h_last_stride < 53 (with h_last);
+ *    h_blocks or h_last not 16-byte aligned; every output NULL.  n_frames == 0 is WCE_OK. */
+#define WCE_TRACK_PHASE    (1u << 0)  /* per-block common pilot phase, as WCE_DEMOD_TRACK */
+#define WCE_TRACK_REF_TX   (1u << 1)  /* EVM against in->tx, as WCE_DEMOD_REF_TX */
+#define WCE_TRACK_KNOWN_TX (1u << 2)  /* x^ = in->tx on every subcarrier: the data-aided bound, nothing decided is fed back */
+
+typedef struct {
+    const wce_complex *h;     /* device; H_0 = h[f*h_stride + k], any estimate (LT_LS, PS_MMSE, H_dd ...) */
+    int64_t h_stride;         /* >= 53 */
+    int32_t modulation;       /* WCE_MOD_*, as wce_demod */
+    uint32_t flags;           /* WCE_TRACK_* */
+    double scale;             /* as wce_demod.scale */
+    double mu;                /* time weight 1/alpha, 0 <= mu <= 1 */
+    int32_t beta;             /* frequency half-window, 0..4 subcarriers */
+} wce_track;
+
+typedef struct {              /* every pointer device, each may be NULL = not wanted; not all */
+    wce_complex *eq;          /* as wce_demod_out */
+    uint8_t *sym;
+    double *theta;
+    double *evm;
+    uint32_t *nerr;
+    int64_t eq_frame_stride, eq_block_stride, sym_frame_stride, sym_block_stride;
+    wce_complex *h_blocks;    /* h_blocks[f*hb_frame_stride + b*hb_block_stride + k] = H_b */
+    int64_t hb_frame_stride, hb_block_stride;
+    wce_complex *h_last;      /* h_last[f*h_last_stride + k] = H_15 */
+    int64_t h_last_stride;
+} wce_track_out;
+
+int wce_track_demodulate(wce_ctx *ctx, const wce_frames *in, const wce_track *p, const wce_track_out *out, void *stream);
+
 /* ---- decoding: soft demapper, deinterleaver, Viterbi decoder (IEEE 802.11-2020
  * 17.3.5.5 to 17.3.5.8; the reference stops at the equalized symbols) ----
  * Every 802.11a/g/p payload is convolutionally coded, punctured and interleaved;
@@ -544,6 +613,13 @@ int wce_demodulate(wce_ctx *ctx, const wce_frames *in, const wce_demod *p, const
  *    bits), ref_stride likewise (with ref_bits); nbiterr without ref_bits; neither bits nor
  *    nbiterr; eq, h or h_lt not 16-byte aligned; llr or nbiterr not 4-byte aligned; n_frames < 0
  *    or > 2^31 - 1.  n_frames == 0 is WCE_OK.
+ *  - wce_soft_demap_blocks is wce_soft_demap with an estimate per block, as a tracked
+ *    receiver has it: Hu_b[k] = hb[f*hb_frame_stride + b*hb_block_stride + k] (wce_track_demodulate's
+ *    h_blocks), 15 more loads per lane, everything else as it is.  Where every block row of a frame
+ *    holds the same h its soft bits are wce_soft_demap's with h_lt = NULL, bit for bit.  The same
+ *    validation: a NULL ctx, eq, hb or llr; an unknown modulation; scale not positive and finite; eq,
+ *    hb or llr strides too small (a row of hb is 53); eq or hb not 16-byte aligned; llr not 4-byte
+ *    aligned; n_frames < 0 or > 2^31 - 1.
  *  - wce_decode_info_bits: T for a modulation and rate, or WCE_EINVAL. */
 enum { WCE_RATE_1_2 = 0, WCE_RATE_2_3 = 1, WCE_RATE_3_4 = 2 };
 #define WCE_DEC_TERMINATED (1u << 0)   /* trace back from state 0 */
@@ -551,6 +627,10 @@ enum { WCE_RATE_1_2 = 0, WCE_RATE_2_3 = 1, WCE_RATE_3_4 = 2 };
 int wce_soft_demap(wce_ctx *ctx, const wce_complex *eq, int64_t eq_frame_stride, int64_t eq_block_stride,
                    const wce_demod *p, int64_t n_frames, float *llr, int64_t llr_frame_stride,
                    int64_t llr_block_stride, void *stream);
+int wce_soft_demap_blocks(wce_ctx *ctx, const wce_complex *eq, int64_t eq_frame_stride, int64_t eq_block_stride,
+                          const wce_complex *hb, int64_t hb_frame_stride, int64_t hb_block_stride,
+                          int32_t modulation, double scale, int64_t n_frames, float *llr, int64_t llr_frame_stride,
+                          int64_t llr_block_stride, void *stream);
 int wce_viterbi_decode(wce_ctx *ctx, const float *llr, int64_t llr_frame_stride, int64_t llr_block_stride,
                        int32_t modulation, int32_t rate, uint32_t flags, int64_t n_frames, uint8_t *bits,
                        int64_t bits_stride, const uint8_t *ref_bits, int64_t ref_stride, uint32_t *nbiterr,
