@@ -1503,7 +1503,12 @@ extern "C" int wce_debug_rank1_rows_per_sweep(wce_ctx *c)
 extern "C" int wce_debug_set_variant(int which, int value)
 {
     const int rc = wce::set_variant(which, value);
-    return rc ? fail(rc, "variant: which in [0, 5), value in [0, 16)") : WCE_OK;
+    return rc ? fail(rc, "variant: which in [0, 7), value in [0, 32)") : WCE_OK;
+}
+
+extern "C" long long wce_debug_chain_grid(long long blocks, long long own_cap)
+{
+    return wce::chain_grid(blocks, own_cap);
 }
 
 extern "C" int wce_debug_set_flat_chunk(long long frames)

@@ -203,8 +203,7 @@ int launch_demap(const DemapArgs &a, void *stream)
     if (a.n <= 0) return WCE_OK;
     if (a.n > 0x7fffffffll) return WCE_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    int64_t blocks = (a.n + DC_WAVES - 1) / DC_WAVES;
-    if (blocks > DC_GRID_CAP) blocks = DC_GRID_CAP;
+    const int64_t blocks = chain_grid((a.n + DC_WAVES - 1) / DC_WAVES, DC_GRID_CAP);
     const dim3 g((uint32_t)blocks), t(64 * DC_WAVES);
     switch (a.mod) {
     case WCE_MOD_BPSK: demap_launch<1>(a, g, t, s); break;
@@ -397,8 +396,7 @@ int launch_viterbi(const ViterbiArgs &a, void *stream)
     }
     if (waves == 0) return WCE_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    int64_t blocks = (a.n + waves - 1) / waves;
-    if (blocks > VT_GRID_CAP) blocks = VT_GRID_CAP;
+    const int64_t blocks = chain_grid((a.n + waves - 1) / waves, VT_GRID_CAP);
     const dim3 g((uint32_t)blocks), t(64 * waves);
     const size_t lds = (size_t)(waves * vt_lds_bytes(a.T));
     switch (a.rate) {

@@ -185,7 +185,7 @@ int launch_demod(const DemodArgs &a, void *stream)
     hipStream_t s = (hipStream_t)stream;
     const int which = (a.eq ? 4 : 0) | (a.sym ? 2 : 0) | ((a.evm || a.nerr) ? 1 : 0);
     int64_t blocks = (a.n + DM_WAVES - 1) / DM_WAVES;
-    if (!(which & 1) && blocks > DM_GRID_CAP) blocks = DM_GRID_CAP;
+    if (!(which & 1)) blocks = chain_grid(blocks, DM_GRID_CAP);   // the builds with the sums have no frame loop
     const dim3 g((uint32_t)blocks);
     switch (which) {
     case 0: demod_launch<false, false, false>(a, g, s); break;   // theta alone

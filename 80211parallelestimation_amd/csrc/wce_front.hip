@@ -106,8 +106,8 @@ int launch_front(const FrontArgs &a, bool preamble, void *stream)
 {
     if (a.n_units == 0) return 0;
     const uint32_t units_per_wg = FE_WAVES * FE_UNITS;
-    uint32_t blocks = (a.n_units + units_per_wg - 1) / units_per_wg;
-    if (blocks > 256u * 40u) blocks = 256u * 40u;   // grid-stride beyond ~40 workgroups per CU
+    // grid-stride beyond ~40 workgroups per CU
+    const uint32_t blocks = (uint32_t)chain_grid((a.n_units + units_per_wg - 1) / units_per_wg, 256 * 40);
     const dim3 grid(blocks), blk(256);
     if (a.start && preamble)
         hipLaunchKernelGGL(front_at_kernel<true>, grid, blk, 0, (hipStream_t)stream, a);

@@ -446,9 +446,25 @@ constexpr int WCE_VARIANT_R1 = 5;      // PS_MMSE with a rank-1 covariance (TEXT
                                       // (R1_VARIANT_ADOPTED) and a launch that is not eligible runs
                                       // mmse_rank1_kernel as under 13; all bit-identical to 0.  2, 5, 6 and 10
                                       // run the general build whatever the State
-constexpr int WCE_VARIANT_COUNT = 6;
+constexpr int WCE_VARIANT_GRID = 6;    // the receive and transmit chain's looping launchers (launch_front, launch_sync,
+                                      // launch_demod's builds without evm / nerr, launch_demap, launch_viterbi,
+                                      // launch_reencode, the three transmit launches): 0 = each its own grid cap
+                                      // (default), else at most CHAIN_TEST_GRID workgroups, so that a few dozen frames
+                                      // make every wave loop over several, the last trip ragged.  A test seam, not an
+                                      // A/B: a frame's outputs depend on its own data alone, so the bits are those of 0.
+                                      // launch_demod's evm / nerr builds and launch_track have no frame loop (a wave
+                                      // per frame on a grid that covers the batch) and never read it
+constexpr int WCE_VARIANT_COUNT = 7;
 int variant_value(int which);
 int set_variant(int which, int value);
+// the workgroups a looping chain launcher starts for `blocks` workgroups of work: at most its own cap, or
+// CHAIN_TEST_GRID under WCE_VARIANT_GRID (wce_debug_chain_grid)
+constexpr int64_t CHAIN_TEST_GRID = 3;
+inline int64_t chain_grid(int64_t blocks, int64_t own_cap)
+{
+    const int64_t cap = variant_value(WCE_VARIANT_GRID) ? CHAIN_TEST_GRID : own_cap;
+    return blocks < cap ? blocks : cap;
+}
 int launch_ldc_convert(const void *src, void *dst, int64_t n, bool to_complex, void *stream);
 int launch_nonfinite_scan(const double *H, int64_t stride, int64_t n, bool f32, uint32_t *bits,
                           unsigned long long *n_bad, void *stream);

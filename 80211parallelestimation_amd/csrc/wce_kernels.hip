@@ -3011,7 +3011,7 @@ constexpr int64_t LR_FPW_BELOW = 131072;
 // 5 63.1 -> 40.8, 6 65.8 -> 46.8, 7 75.4 -> 53.0, 8 68.1 -> 64.4 (before the LDS sharing: rank 4 direct 51.6 vs
 // staged ~60 at 65,536, so 98,304 then)
 constexpr int64_t LR_STAGE_FROM = 0;
-static int g_variant[WCE_VARIANT_COUNT] = {0, 2, 0, 0, 0, 0};
+static int g_variant[WCE_VARIANT_COUNT] = {0, 2, 0, 0, 0, 0, 0};
 int set_variant(int which, int value)
 {
     if (which < 0 || which >= WCE_VARIANT_COUNT || value < 0 || value > 31) return WCE_EINVAL;

@@ -252,8 +252,7 @@ int launch_reencode(const ReencodeArgs &a, void *stream)
     if (a.n <= 0) return WCE_OK;
     if (a.n > 0x7fffffffll || (!a.tx && !a.h) || (a.h && !a.rx)) return WCE_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    int64_t blocks = (a.n + RE_WAVES - 1) / RE_WAVES;
-    if (blocks > RE_GRID_CAP) blocks = RE_GRID_CAP;
+    const int64_t blocks = chain_grid((a.n + RE_WAVES - 1) / RE_WAVES, RE_GRID_CAP);
     const dim3 g((uint32_t)blocks);
     int rc;
     switch (a.mod) {

@@ -190,8 +190,7 @@ __global__ __launch_bounds__(256, SY_WGS_PER_CU) void sync_kernel(SyncArgs a, co
 int launch_sync(const SyncArgs &a, int cus, void *stream)
 {
     if (a.n == 0) return 0;
-    int64_t blocks = (a.n + SY_WAVES - 1) / SY_WAVES;
-    if (blocks > SY_GRID_PER_CU * (int64_t)cus) blocks = SY_GRID_PER_CU * (int64_t)cus;
+    const int64_t blocks = chain_grid((a.n + SY_WAVES - 1) / SY_WAVES, SY_GRID_PER_CU * (int64_t)cus);
     hipLaunchKernelGGL(sync_kernel, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, a,
                        reinterpret_cast<const double2 *>(a.ltf));
     return hipGetLastError() == hipSuccess ? WCE_OK : WCE_EHIP;

@@ -298,7 +298,7 @@ __global__ __launch_bounds__(64) void transmit_kernel(TxArgs a)
     }
 }
 
-static dim3 tx_grid(int64_t n) { return dim3((uint32_t)(n < TX_GRID_CAP ? n : TX_GRID_CAP)); }
+static dim3 tx_grid(int64_t n) { return dim3((uint32_t)chain_grid(n, TX_GRID_CAP)); }
 
 int launch_modulate(const TxArgs &a, void *stream)
 {

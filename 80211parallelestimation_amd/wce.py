@@ -154,6 +154,7 @@ ABI = {
     "wce_debug_set_border_dot": [c_void_p, c_int],
     "wce_debug_set_flat_chunk": [ctypes.c_int64],
     "wce_debug_set_variant": [c_int, c_int],
+    "wce_debug_chain_grid": [c_int64, c_int64],
     "wce_debug_rank1_rows_per_sweep": [c_void_p],
     "wce_debug_rank1_head": [c_int] * 7 + [c_int64] * 3 + [c_int, POINTER(c_int)],
     "wce_debug_rank1_head_groups": [c_uint32, c_uint32, POINTER(c_uint32), c_uint32],
@@ -274,6 +275,8 @@ def load(path: str = LIB_PATH):
     lib.wce_state_size.restype = c_size_t
     if hasattr(lib, "wce_debug_compat_state_builds"):
         lib.wce_debug_compat_state_builds.restype = ctypes.c_ulonglong
+    if hasattr(lib, "wce_debug_chain_grid"):
+        lib.wce_debug_chain_grid.restype = c_int64
     _lib = lib
     return lib
 

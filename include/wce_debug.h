@@ -82,8 +82,24 @@ int wce_debug_set_flat_chunk(long long frames);
  * which 3's kernels sum in different orders and agree to rounding (tests
  * check both); which 5's 0 and 2..19 are bit-identical, 0 and 1 agree to ~1e-11
  * (both within 1e-10 of the long double closed form).  (Round 4 retired ls_flat_kernel -- which 1 = 0, 1 -- and the
- * REF frame tiles -- which 0 = 1.) */
+ * REF frame tiles -- which 0 = 1.)
+ * which 6: the grids of the receive and transmit chain, a test seam rather than
+ * an A/B (0 = every launcher its own cap, default; any other value = at most 3
+ * workgroups, so that a few dozen frames make every wave take several trips
+ * round its frame loop, the last one ragged).  Read by the launchers whose
+ * kernels loop over frames: the front end's six builds, wce_front_end_sync,
+ * wce_demodulate without evm and nerr, wce_soft_demap and _blocks,
+ * wce_viterbi_decode, wce_reencode, wce_modulate, wce_channel, wce_transmit.
+ * A frame's outputs depend on its own data alone, so 1 gives the bits of 0.
+ * Ignored by wce_demodulate with evm or nerr and by wce_track_demodulate:
+ * their kernels run one wave per frame with no loop, on a grid that covers the
+ * batch, and a capped grid would leave frames unvisited.  wce_estimate's
+ * launchers never read it (which 5 = 4 is their capped grid). */
 int wce_debug_set_variant(int which, int value);
+/* What a looping chain launcher makes of `blocks` workgroups of work under its
+ * own cap and the current which 6: min(blocks, own_cap), or min(blocks, 3) with
+ * the knob set.  Needs no device. */
+long long wce_debug_chain_grid(long long blocks, long long own_cap);
 /* (frame, block) units one sweep of mmse_rank1_kernel's persistent grid
  * (which 5 = 7) covers on ctx's device: 16 per workgroup times the workgroups
  * resident at once (4 per CU, the CU count read when ctx was made).  A larger
