@@ -11,7 +11,7 @@ from .wce import (  # noqa: F401
     WiFi_channel_estimation_PS_Linear, WiFi_channel_estimation_PS_MMSE, WiFi_channel_estimation_PS_Sinc,
     DEMOD_REF_TX, DEMOD_TRACK, MOD_BPSK, MOD_QAM16, MOD_QAM64, MOD_QPSK, Demod, DemodOut,
     DEC_TERMINATED, RATE_1_2, RATE_2_3, RATE_3_4, info_bits, ReencodePar, ReencodeOut,
-    ChannelPar, pdp_taps,
+    ChannelPar, FadingPar, pdp_taps, fading_taps,
     TRACK_KNOWN_TX, TRACK_PHASE, TRACK_REF_TX, Track, TrackOut,
 )
 

@@ -1430,6 +1430,88 @@ int wce_transmit(wce_ctx *c, const wce_complex *tx_pre, int64_t pre_stride, cons
     return rc ? fail(rc, "transmit launch") : WCE_OK;
 }
 
+// ---- the time-varying pair: the static calls' checks on the fields the two structures share, then the knots'
+static wce_channel_par static_side(const wce_fading_par *p)
+{
+    return wce_channel_par{nullptr, 0, p->n_taps, p->field, p->cfo, p->ow2, p->delay, p->seed, p->first_frame};
+}
+
+static const char *check_fading(const wce_fading_par *p, wce_complex *capture, int64_t capture_stride,
+                                int64_t capture_len, int64_t n_frames)
+{
+    if (!p) return "null parameters or capture";
+    const wce_channel_par s = static_side(p);
+    if (const char *bad = check_channel(&s, capture, capture_stride, capture_len, n_frames)) return bad;
+    if (!p->knots) return "knots required";
+    if (misaligned(p->knots, 16)) return "knots not 16-byte aligned";
+    if (p->n_knots < 2) return "n_knots < 2";
+    if (p->knot_period < 16 || p->knot_period > (1 << 20)) return "knot_period outside 16..2^20";
+    if (p->knot_stride < p->n_taps) return "knot_stride < n_taps";
+    if (p->frame_stride != 0 && p->frame_stride < (int64_t)(p->n_knots - 1) * p->knot_stride + p->n_taps)
+        return "frame_stride neither 0 nor >= (n_knots - 1) knot_stride + n_taps";
+    return nullptr;
+}
+
+// the knots reach past the last output of a waveform of wave_len samples
+static bool knots_cover(const wce_fading_par *p, int64_t wave_len)
+{
+    return (int64_t)(p->n_knots - 1) * p->knot_period > wave_len + p->n_taps - 2;
+}
+
+static void tx_knots(wce::TxTvArgs &g, const wce_fading_par *p)
+{
+    g.k.knots = reinterpret_cast<const double *>(p->knots); g.k.fs = p->frame_stride; g.k.ks = p->knot_stride;
+    g.k.nk = p->n_knots; g.k.period = p->knot_period;
+}
+
+int wce_channel_tv(wce_ctx *c, const wce_complex *wave, int64_t wave_stride, int64_t wave_len, int64_t n_frames,
+                   const wce_fading_par *p, wce_complex *capture, int64_t capture_stride, int64_t capture_len,
+                   void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    if (!wave) return fail(WCE_EINVAL, "wce_channel_tv: wave required");
+    const char *bad = check_fading(p, capture, capture_stride, capture_len, n_frames);
+    if (bad) return fail(WCE_EINVAL, (std::string("wce_channel_tv: ") + bad).c_str());
+    if (wave_len < 1 || wave_len > 0x7fffffffll) return fail(WCE_EINVAL, "wce_channel_tv: wave_len < 1 or >= 2^31");
+    if (wave_stride < wave_len) return fail(WCE_EINVAL, "wce_channel_tv: wave_stride < wave_len");
+    if (misaligned(wave, 16)) return fail(WCE_EINVAL, "wce_channel_tv: wave not 16-byte aligned");
+    if (!knots_cover(p, wave_len)) return fail(WCE_EINVAL, "wce_channel_tv: the knots do not cover the output");
+    if (n_frames == 0) return WCE_OK;
+    wce::TxTvArgs g{};
+    g.a.wave = reinterpret_cast<const double *>(wave); g.a.ws = wave_stride; g.a.wlen = wave_len; g.a.n = n_frames;
+    const wce_channel_par s = static_side(p);
+    tx_channel(g.a, &s, p->field ? 1 : 0, capture, capture_stride, capture_len);
+    g.a.nt = p->n_taps;
+    tx_knots(g, p);
+    DeviceGuard dg(c->device);
+    const int rc = wce::launch_channel_tv(g, stream);
+    return rc ? fail(rc, "channel_tv launch") : WCE_OK;
+}
+
+int wce_transmit_tv(wce_ctx *c, const wce_complex *tx_pre, int64_t pre_stride, const wce_complex *sym,
+                    int64_t frame_stride, int64_t block_stride, int32_t n_blocks, int64_t n_frames,
+                    const wce_fading_par *p, wce_complex *capture, int64_t capture_stride, int64_t capture_len,
+                    void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    const char *bad = check_symbols(tx_pre, pre_stride, sym, frame_stride, block_stride, n_blocks, n_frames);
+    if (!bad) bad = check_fading(p, capture, capture_stride, capture_len, n_frames);
+    if (bad) return fail(WCE_EINVAL, (std::string("wce_transmit_tv: ") + bad).c_str());
+    if (!knots_cover(p, (tx_pre ? 160 : 0) + 80 * (int64_t)n_blocks))
+        return fail(WCE_EINVAL, "wce_transmit_tv: the knots do not cover the output");
+    if (n_frames == 0) return WCE_OK;
+    wce::TxTvArgs g{};
+    tx_symbols(g.a, tx_pre, pre_stride, sym, frame_stride, block_stride, n_blocks);
+    g.a.n = n_frames;
+    const wce_channel_par s = static_side(p);
+    tx_channel(g.a, &s, g.a.field, capture, capture_stride, capture_len);
+    g.a.nt = p->n_taps;
+    tx_knots(g, p);
+    DeviceGuard dg(c->device);
+    const int rc = wce::launch_transmit_tv(g, stream);
+    return rc ? fail(rc, "transmit_tv launch") : WCE_OK;
+}
+
 // ---------------------------------------------------------------- runtime helpers
 int wce_device_count(int *count)
 {

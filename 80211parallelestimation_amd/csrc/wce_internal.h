@@ -317,9 +317,24 @@ struct TxArgs {
     int64_t first, n;
 };
 
+// the time-varying channel (wce_channel_tv, wce_transmit_tv): TxArgs with taps null and nt = n_taps, and the knots
+// beside it -- a sibling, so that the static kernels keep their argument layout
+struct TxKnots {
+    const double *knots;          // knots[f*fs + k*ks + t], k < nk, t < nt
+    int64_t fs, ks;               // fs 0: one trajectory shared by all frames
+    int32_t nk, period;           // period: samples between knots, 16..2^20
+    int32_t once;                 // set by the launcher: a frame's segments are staged all at once
+};
+struct TxTvArgs {
+    TxArgs a;
+    TxKnots k;
+};
+
 int launch_modulate(const TxArgs &a, void *stream);
 int launch_channel(const TxArgs &a, void *stream);
 int launch_transmit(const TxArgs &a, void *stream);
+int launch_channel_tv(const TxTvArgs &a, void *stream);
+int launch_transmit_tv(const TxTvArgs &a, void *stream);
 int launch_ls(const State *st, const LsArgs &a, void *stream);
 int launch_demod(const DemodArgs &a, void *stream);
 int launch_demap(const DemapArgs &a, void *stream);

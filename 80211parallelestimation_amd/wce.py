@@ -136,6 +136,13 @@ class ChannelPar(ctypes.Structure):
                 ("first_frame", c_int64)]
 
 
+class FadingPar(ctypes.Structure):
+    """struct wce_fading_par (include/wce.h)."""
+    _fields_ = [("knots", c_void_p), ("frame_stride", c_int64), ("knot_stride", c_int64), ("n_knots", c_int32),
+                ("knot_period", c_int32), ("n_taps", c_int32), ("field", c_int32), ("cfo", c_void_p),
+                ("ow2", c_void_p), ("delay", c_void_p), ("seed", c_uint64), ("first_frame", c_int64)]
+
+
 _lib = None
 
 # (name, argtypes) for every symbol include/wce.h and include/wce_compat.h declare
@@ -211,6 +218,10 @@ ABI = {
                     c_void_p],
     "wce_transmit": [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int64, POINTER(ChannelPar),
                      c_void_p, c_int64, c_int64, c_void_p],
+    "wce_channel_tv": [c_void_p, c_void_p, c_int64, c_int64, c_int64, POINTER(FadingPar), c_void_p, c_int64, c_int64,
+                       c_void_p],
+    "wce_transmit_tv": [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int64,
+                        POINTER(FadingPar), c_void_p, c_int64, c_int64, c_void_p],
     "wce_nonfinite_scan": [c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int64, c_uint32, c_void_p, c_void_p,
                            c_void_p],
     "wce_comm_unique_id": [c_void_p],
@@ -750,13 +761,59 @@ class Context:
                                  capture_stride if capture_stride is not None else capture_len, capture_len, stream),
                "wce_transmit")
 
+    @staticmethod
+    def _fading_par(knots, n_knots, knot_period, n_taps, knot_stride, knots_frame_stride, field, cfo, ow2, delay,
+                    seed, first_frame):
+        return FadingPar(_addr(knots), knots_frame_stride, knot_stride if knot_stride is not None else n_taps,
+                         n_knots, knot_period, n_taps, int(bool(field)), _addr(cfo), _addr(ow2), _addr(delay), seed,
+                         first_frame)
+
+    def channel_tv(self, wave, n_frames, wave_len, capture, capture_len, knots, n_knots, knot_period=80, n_taps=1,
+                   knot_stride=None, knots_frame_stride=0, field=True, cfo=None, ow2=None, delay=None, seed=0x80211,
+                   first_frame=0, wave_stride=None, capture_stride=None, stream=None):
+        """wce_channel_tv on device arrays: channel with taps that move within the packet.  knots complex
+        [n][knots_frame_stride] (0: one trajectory [n_knots][knot_stride] shared by all frames), n_knots sets of
+        n_taps taps knot_period samples apart, the first under the waveform's first sample; a tap is interpolated
+        linearly between its knots, and the knots must reach past the last output: (n_knots - 1) knot_period >
+        wave_len + n_taps - 2.  knot_stride defaults to n_taps.  Everything else as channel; constant knots give
+        channel's bits."""
+        p = self._fading_par(knots, n_knots, knot_period, n_taps, knot_stride, knots_frame_stride, field, cfo, ow2,
+                             delay, seed, first_frame)
+        _check(_lib.wce_channel_tv(self.handle, _addr(wave), wave_stride if wave_stride is not None else wave_len,
+                                   wave_len, n_frames, byref(p), _addr(capture),
+                                   capture_stride if capture_stride is not None else capture_len, capture_len,
+                                   stream), "wce_channel_tv")
+
+    def transmit_tv(self, sym, n_frames, capture, capture_len, knots, n_knots, knot_period=80, n_taps=1,
+                    knot_stride=None, knots_frame_stride=0, n_blocks=NBLK, tx_pre=None, pre_stride=0,
+                    frame_stride=None, block_stride=NSC, cfo=None, ow2=None, delay=None, seed=0x80211, first_frame=0,
+                    capture_stride=None, stream=None):
+        """wce_transmit_tv on device arrays: modulate and channel_tv in one launch, the bits of the two calls in
+        sequence.  Arguments as transmit's and channel_tv's; a full packet at knot_period 80 takes 19 knots."""
+        p = self._fading_par(knots, n_knots, knot_period, n_taps, knot_stride, knots_frame_stride,
+                             tx_pre is not None, cfo, ow2, delay, seed, first_frame)
+        _check(_lib.wce_transmit_tv(self.handle, _addr(tx_pre), pre_stride, _addr(sym),
+                                    frame_stride if frame_stride is not None else n_blocks * block_stride,
+                                    block_stride, n_blocks, n_frames, byref(p), _addr(capture),
+                                    capture_stride if capture_stride is not None else capture_len, capture_len,
+                                    stream), "wce_transmit_tv")
+
     def _transmit_device(self, dsym, B, n_blocks, dpre, pre_stride, taps, cfo, ow2, delay, capture_len, seed,
-                         first_frame, fused):
+                         first_frame, fused, knot_period=None):
         """transmit_host's device half: symbols (and the preamble) on the device, the channel's per-frame
         parameters on the host -> (capture DeviceArray [B][capture_len], what the queued calls read until the
-        caller synchronises)"""
+        caller synchronises).  Taps with a knot axis ([B][K][n_taps], or [K][n_taps] with knot_period given) go
+        through the time-varying calls."""
         dtaps, n_taps, ts = None, 1, 0
-        if taps is not None:
+        tv = taps is not None and (np.ndim(taps) == 3 or (np.ndim(taps) == 2 and knot_period is not None))
+        if tv:
+            taps = _as_c128(taps)
+            if taps.ndim == 3 and taps.shape[0] != B:
+                raise ValueError("taps with knots must be [K][n_taps] or [B][K][n_taps] complex")
+            n_knots, n_taps = taps.shape[-2], taps.shape[-1]
+            kfs = n_knots * n_taps if taps.ndim == 3 else 0
+            dtaps = DeviceArray.from_numpy(taps)
+        elif taps is not None:
             taps = _as_c128(taps)
             if taps.ndim not in (1, 2) or (taps.ndim == 2 and taps.shape[0] != B):
                 raise ValueError("taps must be [n_taps] or [B][n_taps] complex")
@@ -771,7 +828,19 @@ class Context:
         S = (160 if dpre is not None else 0) + SAMPLES_PER_BLOCK * n_blocks
         dcap = DeviceArray((B, capture_len), zero=True)
         keep = [dtaps, dcfo, dow2, ddelay]
-        if fused:
+        if tv:
+            P = 80 if knot_period is None else int(knot_period)
+            kn = dict(knots=dtaps, n_knots=n_knots, knot_period=P, n_taps=n_taps, knot_stride=n_taps,
+                      knots_frame_stride=kfs, cfo=dcfo, ow2=dow2, delay=ddelay, seed=seed, first_frame=first_frame)
+            if fused:
+                self.transmit_tv(dsym, B, dcap, capture_len, n_blocks=n_blocks, tx_pre=dpre, pre_stride=pre_stride,
+                                 **kn)
+            else:
+                dwave = DeviceArray((B, S), zero=True)
+                keep.append(dwave)
+                self.modulate(dsym, B, dwave, n_blocks, dpre, pre_stride)
+                self.channel_tv(dwave, B, S, dcap, capture_len, field=dpre is not None, **kn)
+        elif fused:
             self.transmit(dsym, B, dcap, capture_len, n_blocks, dpre, pre_stride, taps=dtaps, n_taps=n_taps,
                           taps_stride=ts, cfo=dcfo, ow2=dow2, delay=ddelay, seed=seed, first_frame=first_frame)
         else:
@@ -783,12 +852,15 @@ class Context:
         return dcap, keep
 
     def transmit_host(self, sym, tx_pre=None, taps=None, cfo=None, ow2=None, delay=None, capture_len=None,
-                      seed=0x80211, first_frame=0, fused=True):
+                      seed=0x80211, first_frame=0, fused=True, knot_period=None):
         """Convenience: host symbols sym [B][n_blocks][53] (n_blocks 0..15) and, optionally, the preamble's 53
         bins tx_pre ([53] shared, or [B][53]) -> raw capture windows [B][capture_len] on the host.  taps [n_taps]
         or [B][n_taps] complex (None: a unit tap); cfo (cycles per sample), ow2 (noise variance per complex
         sample) and delay (int, any sign): a scalar or [B], None = 0.  capture_len defaults to the waveform's
-        length plus the taps' tail.  fused: one transmit launch, else modulate then channel -- the same bits."""
+        length plus the taps' tail.  fused: one transmit launch, else modulate then channel -- the same bits.
+        Taps that move within the packet (transmit_tv; fading_taps draws them): [B][K][n_taps], K knots
+        knot_period samples apart (None: 80, a knot per block boundary, K = 19 for a full packet), or one shared
+        trajectory [K][n_taps], which needs knot_period given: without it 2-D taps are [B][n_taps]."""
         sym = _as_c128(sym)
         if sym.ndim != 3 or sym.shape[2] != NSC or sym.shape[1] > NBLK:
             raise ValueError("sym must be [B][n_blocks <= 15][53] complex")
@@ -804,13 +876,13 @@ class Context:
             capture_len = (160 if dpre is not None else 0) + SAMPLES_PER_BLOCK * n_blocks + \
                 (np.shape(taps)[-1] if taps is not None else 1) - 1
         dcap, keep = self._transmit_device(dsym, B, n_blocks, dpre, ps, taps, cfo, ow2, delay, int(capture_len), seed,
-                                           first_frame, fused)
+                                           first_frame, fused, knot_period)
         synchronize()
         return dcap.numpy()
 
     def link_host(self, modulation, rate, snr_db, n_frames, sources=(LT_LS, PS_LINEAR, PS_MMSE), taps=None, cfo=None,
                   delay=None, capture_len=1488, threshold=0.25, backoff=0, seed=0x80211, dd_iterations=0,
-                  scale=8.8753):
+                  scale=8.8753, knot_period=80, tracker=None):
         """The experiment WiFi_RX.m:4-9 announces (SNR, channel_model, FO), for a batch, scored in coded bit
         errors: n_frames packets of random information bits (drawn on the host from `seed`, the last six 0) are
         re-encoded to symbols with 802.11's pilots, transmitted behind the context's tx preamble through `taps`
@@ -826,9 +898,18 @@ class Context:
         context's ow2 and covariance otherwise.
         dd_iterations n > 0: n decision-directed rounds behind each source's decoder; its count is the last
         round's.
+        taps [B][K][n_taps] (fading_taps draws them): a channel that moves within the packet, K knots
+        knot_period samples apart, through transmit_tv.  tracker (mu, beta): each source's estimate additionally
+        starts a track_demodulate (no blend, phase tracking on) on the same capture, followed by
+        soft_demap_blocks on its h_blocks and viterbi_decode; not together with dd_iterations.
         -> {source: nbiterr uint32 [B]} plus "start" int32 [B] (-1: not detected; its counts are those of an
-        all-zero decode), "metric" [B], "cfo" [B] (the estimate), "ow2" [B] and "bits" uint8 [B][T]."""
+        all-zero decode), "metric" [B], "cfo" [B] (the estimate), "ow2" [B] and "bits" uint8 [B][T]; with
+        tracker, "tracked": {source: nbiterr uint32 [B]} of the tracked runs."""
         B, T = int(n_frames), info_bits(modulation, rate)
+        if tracker is not None and dd_iterations:
+            raise ValueError("tracker with dd_iterations > 0 (decoder-in-the-loop tracking) is not built")
+        if tracker is not None:
+            mu, beta = tracker
         if self.tx_pre is None:
             raise ValueError("link_host needs a context built from a tx preamble")
         names = {LT_LS: "lt_ls", PS_LINEAR: "ps_linear", PS_CUBIC: "ps_cubic", PS_SINC: "ps_sinc", PS_MMSE: "ps_mmse"}
@@ -847,7 +928,7 @@ class Context:
         self.reencode(dbits, B, modulation, rate, scale, tx=dtx)
         self.modulate(None, 1, dfield, 0, dpre)
         dcap, keep = self._transmit_device(dtx, B, NBLK, dpre, 0, taps, cfo, ow2, delay, int(capture_len), seed, 0,
-                                           True)
+                                           True, knot_period if np.ndim(taps) == 3 else None)
         dstart, dmetric = DeviceArray((B,), np.int32, zero=True), DeviceArray((B,), np.float64, zero=True)
         dow2e, dcfo = DeviceArray((B,), np.float64, zero=True), DeviceArray((B,), np.float64, zero=True)
         drx, drxpre = DeviceArray((B, NBLK, NSC), zero=True), DeviceArray((B, NSC), zero=True)
@@ -874,8 +955,16 @@ class Context:
             dd = self._dd_device(fr, B, dec["bits"], dem["theta"], modulation, rate, scale, True, dec["_ref"],
                                  int(dd_iterations)) if dd_iterations else None
             runs[s] = (dem, dec, dd)
+        tracked = {}
+        if tracker is not None:
+            for s in sources:
+                trk = self._track_device(fr, B, outs[names[s]], mu, beta, modulation, scale, True, True)
+                tracked[s] = (trk, self._decode_device(trk["eq"], None, None, B, modulation, rate, scale, True, bits,
+                                                       h_blocks=trk["h_blocks"]))
         synchronize()
         res = {s: (dd if dd is not None else dec)["nbiterr"].numpy() for s, (dem, dec, dd) in runs.items()}
+        if tracker is not None:
+            res["tracked"] = {s: dec["nbiterr"].numpy() for s, (trk, dec) in tracked.items()}
         res.update(start=dstart.numpy(), metric=dmetric.numpy(), cfo=dcfo.numpy(), ow2=ow2, bits=bits)
         return res
 
@@ -1348,6 +1437,32 @@ def pdp_taps(rng, n_frames, power) -> np.ndarray:
     h = (rng.standard_normal((n_frames, power.size)) + 1j * rng.standard_normal((n_frames, power.size))) * \
         np.sqrt(power / 2)
     return h / np.sqrt(np.sum(np.abs(h) ** 2, axis=1, keepdims=True))
+
+
+def fading_taps(rng, n_frames, power, rho, n_knots) -> np.ndarray:
+    """Tap trajectories for Context.transmit_host / link_host (3-D taps): knot 0 is pdp_taps(rng, n_frames, power),
+    drawn from the same generator state in the same order and normalised the same way, and each further knot is
+    the Gauss-Markov step  knot k+1 = rho knot k + sqrt(1 - rho^2) w c,  w drawn CN(0, power) per tap and c the
+    factor that normalised knot 0 -- so every knot of a tap has the variance of knot 0 and neighbouring knots
+    correlate by rho.  rho in [0, 1]: 1.0 freezes the channel (every knot is knot 0, bit for bit).
+    -> complex [n_frames][n_knots][len(power)]; the transmitter interpolates linearly between the knots."""
+    if not 0.0 <= rho <= 1.0:
+        raise ValueError("rho must lie in [0, 1]")
+    if n_knots < 2:
+        raise ValueError("n_knots must be at least 2")
+    power = np.asarray(power, np.float64)
+    if power.ndim != 1 or not 1 <= power.size <= 16 or np.any(power < 0) or not power.sum() > 0:
+        raise ValueError("power must hold 1..16 non-negative tap powers")
+    shape = (n_frames, power.size)
+    h = (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)) * np.sqrt(power / 2)
+    c = 1.0 / np.sqrt(np.sum(np.abs(h) ** 2, axis=1, keepdims=True))
+    out = np.empty((n_frames, n_knots, power.size), np.complex128)
+    out[:, 0] = h / np.sqrt(np.sum(np.abs(h) ** 2, axis=1, keepdims=True))
+    step = np.sqrt(1.0 - rho * rho)
+    for k in range(1, n_knots):
+        w = (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)) * np.sqrt(power / 2)
+        out[:, k] = rho * out[:, k - 1] + step * w * c
+    return out
 
 
 def state_blob(tx_pre, rx_pre, ow2, mode=MMSE_REF, Rhh=None) -> np.ndarray:

@@ -781,6 +781,65 @@ int wce_transmit(wce_ctx *ctx, const wce_complex *tx_pre, int64_t pre_stride, co
                  const wce_channel_par *p, wce_complex *capture, int64_t capture_stride, int64_t capture_len,
                  void *stream);
 
+/* ---- a channel that fades within the packet: wce_channel_tv, wce_transmit_tv ----
+ * wce_channel and wce_transmit hold one set of taps per frame for the whole packet.  These
+ * two calls are theirs with taps that move sample by sample: each tap is interpolated
+ * linearly between knots, n_knots sets of n_taps taps knot_period (P) samples apart.  The
+ * channel travels with the packet: knot k sits at waveform-output sample m = k P, m = 0
+ * being the output under the first clean sample, whatever delay[f] is.
+ * For 0 <= m < wave_len + n_taps - 1, with a[k][t] = knots[f*frame_stride + k*knot_stride + t]:
+ *   k = floor(m / P),  j = m - k P                          (an integer below P: exact)
+ *   d[k][t] = (a[k+1][t] - a[k][t]) / P                     real and imaginary part each: one fp64
+ *                                                           subtraction, one fp64 division
+ *   h_t(m)  = ( fma(j, d.re, a[k][t].re), fma(j, d.im, a[k][t].im) )
+ *   y[m]    = sum_{t < n_taps, t ascending} h_t(m) s[m - t]  wce_channel's two fmas a part
+ * and the rotor, the placement by delay[f], the clipping and the noise are wce_channel's, word
+ * for word; the noise depends on (seed, first_frame + f, i) only, so the same seed gives a
+ * static and a fading channel the same noise.
+ *   cover     the knots cover every output, nothing is extrapolated:
+ *             (n_knots - 1) P > wave_len + n_taps - 2; the smallest such count is
+ *             floor((wave_len + n_taps - 2) / P) + 2: 19 knots for a full packet (1,360 samples)
+ *             at P = 80, one at every block boundary, two segments under the field.  Knots beyond
+ *             the last output's segment are read by the guard only.
+ *   guard     wce_channel's, and a frame one of whose n_knots x n_taps knot values is not finite,
+ *             used by an output or not: NaN in every sample of its window; no other frame changes
+ *             by a bit.
+ *   constant  where every knot of a frame equals h[t] (and no part of h is a negative zero),
+ *             d is +0 and h_t(m) is h[t] exactly: that frame's window is wce_channel's (or
+ *             wce_transmit's) with taps = h, bit for bit.
+ *   fused     wce_transmit_tv is wce_modulate followed by wce_channel_tv on the same arguments,
+ *             bit for bit (p->field is ignored, as in wce_transmit).
+ *  - Asynchronous on `stream`, nothing read back, nothing allocated, as the static calls; a
+ *    frame's bits depend only on its own data, its knots, first_frame + f and the arguments.
+ *  - WCE_EINVAL before any launch: every refusal of wce_channel (for wce_channel_tv) or
+ *    wce_transmit (for wce_transmit_tv) that does not concern taps, and: knots NULL or not
+ *    16-byte aligned; n_knots < 2; knot_period outside 16..2^20 (16 is the cyclic prefix: a
+ *    run of 8 outputs then meets one knot at most); knot_stride < n_taps; frame_stride neither
+ *    0 nor >= (n_knots - 1) knot_stride + n_taps; knots that do not cover the output.
+ *    n_frames == 0 is WCE_OK. */
+typedef struct {
+    const wce_complex *knots; /* device; knots[f*frame_stride + k*knot_stride + t], k < n_knots, t < n_taps */
+    int64_t frame_stride;     /* >= (n_knots - 1) knot_stride + n_taps; 0 = one trajectory shared by all frames */
+    int64_t knot_stride;      /* >= n_taps */
+    int32_t n_knots;          /* >= 2, and enough to cover the output */
+    int32_t knot_period;      /* P, samples between knots: 16..2^20 */
+    int32_t n_taps;           /* 1..16 */
+    int32_t field;            /* as wce_channel_par's, and so are the five below */
+    const double *cfo;
+    const double *ow2;
+    const int32_t *delay;
+    uint64_t seed;
+    int64_t first_frame;
+} wce_fading_par;
+
+int wce_channel_tv(wce_ctx *ctx, const wce_complex *wave, int64_t wave_stride, int64_t wave_len, int64_t n_frames,
+                   const wce_fading_par *p, wce_complex *capture, int64_t capture_stride, int64_t capture_len,
+                   void *stream);
+int wce_transmit_tv(wce_ctx *ctx, const wce_complex *tx_pre, int64_t pre_stride, const wce_complex *sym,
+                    int64_t frame_stride, int64_t block_stride, int32_t n_blocks, int64_t n_frames,
+                    const wce_fading_par *p, wce_complex *capture, int64_t capture_stride, int64_t capture_len,
+                    void *stream);
+
 /* Non-finite guard.  The reference passes NaN/Inf through
  * silently: main.c's PS_MMSE returns NaN x 53 (main.c:148-212), a zero pilot
  * makes PS_* divide by zero (main.c:82-84), and its dimension checks only
