@@ -1,6 +1,7 @@
 // wce_api.cpp -- C ABI (include/wce.h): context lifetime, argument checks,
 // launches, and thin HIP runtime helpers.
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -1014,6 +1015,56 @@ int wce_front_end_sync(wce_ctx *c, const wce_complex *capture, int64_t capture_s
     return rc ? fail(rc, "sync launch") : WCE_OK;
 }
 
+int wce_front_end_sync_stf(wce_ctx *c, const wce_complex *capture, int64_t capture_stride, int64_t capture_len,
+                           int64_t n_frames, const wce_complex *ltf, double threshold_stf, double threshold_ltf,
+                           int32_t backoff, int32_t *start, double *cfo, double *metric_stf, double *metric_ltf,
+                           void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    if (n_frames < 0) return fail(WCE_EINVAL, "n_frames < 0");
+    if (capture_len < 2 * WCE_FFT_SIZE + 16 || capture_len >= (int64_t)1 << 31)
+        return fail(WCE_EINVAL, "capture_len outside [144, 2^31)");
+    if (capture_stride < capture_len) return fail(WCE_EINVAL, "capture_stride < capture_len");
+    if (!(threshold_stf >= 0.0 && threshold_stf <= 1.0)) return fail(WCE_EINVAL, "threshold_stf outside [0, 1]");
+    if (!(threshold_ltf >= 0.0 && threshold_ltf <= 1.0)) return fail(WCE_EINVAL, "threshold_ltf outside [0, 1]");
+    if (backoff < 0 || backoff > 31) return fail(WCE_EINVAL, "backoff outside [0, 31]");
+    if (!start || reinterpret_cast<uintptr_t>(start) % 4) return fail(WCE_EINVAL, "start null or not 4-byte aligned");
+    if (!cfo || reinterpret_cast<uintptr_t>(cfo) % 8) return fail(WCE_EINVAL, "cfo null or not 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(metric_stf) % 8 || reinterpret_cast<uintptr_t>(metric_ltf) % 8)
+        return fail(WCE_EINVAL, "metric not 8-byte aligned");
+    if (!ltf || reinterpret_cast<uintptr_t>(ltf) % 16) return fail(WCE_EINVAL, "ltf null or not 16-byte aligned");
+    if (!capture || reinterpret_cast<uintptr_t>(capture) % 16)
+        return fail(WCE_EINVAL, "capture null or not 16-byte aligned");
+    if (n_frames == 0) return WCE_OK;
+    wce::SyncStfArgs a{};
+    a.capture = reinterpret_cast<const double *>(capture);
+    a.ltf = reinterpret_cast<const double *>(ltf);
+    a.stride = capture_stride; a.len = capture_len; a.n = n_frames;
+    a.threshold_stf = threshold_stf; a.threshold_ltf = threshold_ltf; a.backoff = backoff;
+    a.start = start; a.cfo = cfo; a.metric_stf = metric_stf; a.metric_ltf = metric_ltf;
+    DeviceGuard g(c->device);
+    int rc = wce::launch_sync_stf(a, c->cus, stream);
+    return rc ? fail(rc, "sync_stf launch") : WCE_OK;
+}
+
+int wce_short_field(wce_ctx *c, double amplitude, wce_complex *wave, int64_t wave_stride, int64_t n_frames,
+                    void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    if (n_frames < 0) return fail(WCE_EINVAL, "n_frames < 0");
+    if (!wave || reinterpret_cast<uintptr_t>(wave) % 16) return fail(WCE_EINVAL, "wave null or not 16-byte aligned");
+    if (wave_stride < wce::SHORT_FIELD_LEN) return fail(WCE_EINVAL, "wave_stride < 160");
+    if (!std::isfinite(amplitude)) return fail(WCE_EINVAL, "amplitude not finite");
+    if (n_frames == 0) return WCE_OK;
+    wce::ShortFieldArgs a{};
+    a.wave = reinterpret_cast<double *>(wave);
+    a.stride = wave_stride; a.n = n_frames; a.amplitude = amplitude;
+    wce::short_field_period(a.t);
+    DeviceGuard g(c->device);
+    int rc = wce::launch_short_field(a, c->cus, stream);
+    return rc ? fail(rc, "short field launch") : WCE_OK;
+}
+
 // ---------------------------------------------------------------- demodulation
 int wce_demodulate(wce_ctx *c, const wce_frames *in, const wce_demod *p, const wce_demod_out *out, void *stream)
 {
@@ -1593,6 +1644,20 @@ extern "C" long long wce_debug_chain_grid(long long blocks, long long own_cap)
     return wce::chain_grid(blocks, own_cap);
 }
 
+extern "C" int wce_debug_short_field_period(double *out)
+{
+    if (!out) return fail(WCE_EINVAL, "null buffer");
+    wce::short_field_period(out);
+    return WCE_OK;
+}
+
+extern "C" int wce_debug_sync_stf_tiles(int *lags_stf, int *lags_ltf)
+{
+    if (!lags_stf || !lags_ltf) return fail(WCE_EINVAL, "null buffer");
+    wce::sync_stf_tiles(lags_stf, lags_ltf);
+    return WCE_OK;
+}
+
 extern "C" int wce_debug_set_flat_chunk(long long frames)
 {
     const int rc = wce::set_flat_chunk(frames);
@@ -1604,4 +1669,26 @@ namespace wce {
 int api_fail(int code, const char *what) { return fail(code, what); }
 int ctx_device(const wce_ctx *c) { return c ? c->device : -1; }
 bool ctx_ready(const wce_ctx *c) { return c && c->ready; }
+
+// 802.11a's short sequence on the bins k = -24, -20 .. 24 without DC: the signs of sqrt(13/6) (1 + j)
+static const int kShortSign[12] = {+1, -1, +1, -1, -1, +1, -1, -1, +1, +1, +1, +1};
+
+void short_field_period(double *t32)
+{
+    const long double pi = 3.14159265358979323846264338327950288L;
+    const long double amp = sqrtl(13.0L / 6.0L) / 64.0L;
+    for (int m = 0; m < 16; ++m) {
+        // t[m] = (1/64) sum_k S_k exp(2 pi i k m / 64), k = 4 j: the twiddle's argument is (j m mod 16) / 16 of a turn
+        long double re = 0.0L, im = 0.0L;
+        for (int i = 0; i < 12; ++i) {
+            const int j = i < 6 ? i - 6 : i - 5;
+            const int turn = ((j * m) % 16 + 16) % 16;
+            const long double cs = cosl(2.0L * pi * turn / 16.0L), sn = sinl(2.0L * pi * turn / 16.0L);
+            re += kShortSign[i] * (cs - sn);   // (1 + j) (cs + j sn)
+            im += kShortSign[i] * (cs + sn);
+        }
+        t32[2 * m] = (double)(amp * re);
+        t32[2 * m + 1] = (double)(amp * im);
+    }
+}
 }  // namespace wce

@@ -224,6 +224,27 @@ struct SyncArgs {
     double *metric;       // may be null
 };
 
+// detection on the short training field, coarse offset, timing on the derotated long field, unwrapped fine offset
+// (wce_sync_stf.hip): windows as SyncArgs
+struct SyncStfArgs {
+    const double *capture, *ltf;
+    int64_t stride, len, n;
+    double threshold_stf, threshold_ltf;
+    int32_t backoff;
+    int32_t *start;
+    double *cfo;
+    double *metric_stf, *metric_ltf;   // each may be null
+};
+
+// the transmitter's short training field (wce_sync_stf.hip): wave[f*stride + m] = amplitude t[m mod 16], m < 160
+constexpr int SHORT_FIELD_LEN = 160;
+struct ShortFieldArgs {
+    double *wave;
+    int64_t stride, n;
+    double amplitude;
+    double t[32];         // the period's 16 samples {re, im} (short_field_period)
+};
+
 // demodulation (wce_demod.hip): frames as LsArgs; h / hlt rows of stride hs (hlt null: no blend)
 struct DemodArgs {
     const double *tx, *rx, *h, *hlt;
@@ -348,6 +369,14 @@ int decode_info_bits(int mod, int rate);
 int launch_front(const FrontArgs &a, bool preamble, void *stream);
 // cus: the device's CU count, which caps the grid
 int launch_sync(const SyncArgs &a, int cus, void *stream);
+int launch_sync_stf(const SyncStfArgs &a, int cus, void *stream);
+// lags one tile of sync_stf_kernel covers in its first and its second pass (wce_debug_sync_stf_tiles)
+void sync_stf_tiles(int *lags_stf, int *lags_ltf);
+int launch_short_field(const ShortFieldArgs &a, int cus, void *stream);
+// one period of 802.11a's short training symbol at amplitude 1, 16 {re, im} pairs: the 64-point inverse DFT
+// (1/64) of sqrt(13/6) (1 + j) s_k on the bins k = -24, -20 .. 24 without DC, summed in 80-bit arithmetic
+// with exact twiddle arguments and rounded to double (wce_api.cpp; wce_debug_short_field_period)
+void short_field_period(double *t32);
 // PS_MMSE solve launchers: each starts the one kernel family the route (wce_route.h) names.
 // REF pilot form, C semantics (mmse_ref_flat_kernel / mmse_ref_elem_kernel by batch size)
 int launch_mmse_ref_pilots(const State *st, const SolveArgs &a, void *stream);
@@ -462,6 +491,7 @@ constexpr int WCE_VARIANT_R1 = 5;      // PS_MMSE with a rank-1 covariance (TEXT
                                       // mmse_rank1_kernel as under 13; all bit-identical to 0.  2, 5, 6 and 10
                                       // run the general build whatever the State
 constexpr int WCE_VARIANT_GRID = 6;    // the receive and transmit chain's looping launchers (launch_front, launch_sync,
+                                      // launch_sync_stf, launch_short_field,
                                       // launch_demod's builds without evm / nerr, launch_demap, launch_viterbi,
                                       // launch_reencode, the three transmit launches): 0 = each its own grid cap
                                       // (default), else at most CHAIN_TEST_GRID workgroups, so that a few dozen frames

@@ -40,6 +40,7 @@ MMSE_TEXTBOOK = 1
 MMSE_COV = 2       # TEXTBOOK with a caller-supplied channel covariance Rhh
 FFT_SIZE = 64            # front end: 64-point DFT per OFDM block (WiFi_RX.m:10)
 SAMPLES_PER_BLOCK = 80   # 64 + 16-sample cyclic prefix (WiFi_RX.m:12)
+STF_LEN = 160            # short training field: ten periods of 16 samples (wce_short_field)
 SEM_C = 0          # main.c semantics
 SEM_MATLAB = 1     # WiFi_channel_estimation_*.m semantics
 MOD_BPSK, MOD_QPSK, MOD_QAM16, MOD_QAM64 = 1, 2, 4, 6   # wce_demod.modulation: bits per data symbol
@@ -198,6 +199,11 @@ ABI = {
                                    c_void_p, c_int, c_void_p],
     "wce_front_end_sync": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_double, c_int32, c_void_p,
                            c_void_p, c_void_p],
+    "wce_front_end_sync_stf": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_double, c_double, c_int32,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "wce_short_field": [c_void_p, c_double, c_void_p, c_int64, c_int64, c_void_p],
+    "wce_debug_short_field_period": [c_void_p],
+    "wce_debug_sync_stf_tiles": [POINTER(c_int), POINTER(c_int)],
     "wce_front_end_preamble_at": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                   c_void_p, c_void_p, c_int, c_void_p],
     "wce_front_end_blocks_at": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64,
@@ -728,6 +734,21 @@ class Context:
                                  n_blocks, n_frames, _addr(wave), wave_stride if wave_stride is not None else S,
                                  stream), "wce_modulate")
 
+    def short_field(self, wave, n_frames, amplitude=1.0, wave_stride=STF_LEN, stream=None):
+        """wce_short_field on a device array: wave complex [n][wave_stride], whose first 160 samples of each row
+        become 802.11a's short training field at `amplitude` (1: the mean sample power of a long field of unit
+        bins, 52/4096).  A packet with a short field: this, then modulate from wave + 160 samples, then channel
+        with wave_len 1520."""
+        _check(_lib.wce_short_field(self.handle, amplitude, _addr(wave), wave_stride, n_frames, stream),
+               "wce_short_field")
+
+    def stf_amplitude(self):
+        """the short field's amplitude that matches the context's tx preamble: the rms of its non-zero bins"""
+        if self.tx_pre is None:
+            raise ValueError("the context has no tx preamble")
+        p = np.abs(np.asarray(self.tx_pre).ravel())
+        return float(np.sqrt(np.mean(p[p != 0] ** 2)))
+
     @staticmethod
     def _channel_par(taps, n_taps, taps_stride, field, cfo, ow2, delay, seed, first_frame):
         return ChannelPar(_addr(taps), taps_stride, n_taps, int(bool(field)), _addr(cfo), _addr(ow2), _addr(delay),
@@ -799,11 +820,14 @@ class Context:
                                     stream), "wce_transmit_tv")
 
     def _transmit_device(self, dsym, B, n_blocks, dpre, pre_stride, taps, cfo, ow2, delay, capture_len, seed,
-                         first_frame, fused, knot_period=None):
+                         first_frame, fused, knot_period=None, stf=False):
         """transmit_host's device half: symbols (and the preamble) on the device, the channel's per-frame
         parameters on the host -> (capture DeviceArray [B][capture_len], what the queued calls read until the
         caller synchronises).  Taps with a knot axis ([B][K][n_taps], or [K][n_taps] with knot_period given) go
-        through the time-varying calls."""
+        through the time-varying calls.  stf: the short field in front (short_field, modulate 160 samples in,
+        channel over the 1,520 samples; never fused)."""
+        if stf and dpre is None:
+            raise ValueError("stf needs a tx preamble: the short field goes in front of the long one")
         dtaps, n_taps, ts = None, 1, 0
         tv = taps is not None and (np.ndim(taps) == 3 or (np.ndim(taps) == 2 and knot_period is not None))
         if tv:
@@ -828,6 +852,18 @@ class Context:
         S = (160 if dpre is not None else 0) + SAMPLES_PER_BLOCK * n_blocks
         dcap = DeviceArray((B, capture_len), zero=True)
         keep = [dtaps, dcfo, dow2, ddelay]
+
+        def wave():   # the clean waveform, unfused: [short field,] long field, blocks
+            W = S + (STF_LEN if stf else 0)
+            dwave = DeviceArray((B, W), zero=True)
+            keep.append(dwave)
+            if stf:
+                self.short_field(dwave, B, self.stf_amplitude(), W)
+                self.modulate(dsym, B, dwave.addr + STF_LEN * 16, n_blocks, dpre, pre_stride, wave_stride=W)
+            else:
+                self.modulate(dsym, B, dwave, n_blocks, dpre, pre_stride)
+            return dwave, W
+        fused = fused and not stf
         if tv:
             P = 80 if knot_period is None else int(knot_period)
             kn = dict(knots=dtaps, n_knots=n_knots, knot_period=P, n_taps=n_taps, knot_stride=n_taps,
@@ -836,23 +872,19 @@ class Context:
                 self.transmit_tv(dsym, B, dcap, capture_len, n_blocks=n_blocks, tx_pre=dpre, pre_stride=pre_stride,
                                  **kn)
             else:
-                dwave = DeviceArray((B, S), zero=True)
-                keep.append(dwave)
-                self.modulate(dsym, B, dwave, n_blocks, dpre, pre_stride)
-                self.channel_tv(dwave, B, S, dcap, capture_len, field=dpre is not None, **kn)
+                dwave, W = wave()
+                self.channel_tv(dwave, B, W, dcap, capture_len, field=dpre is not None, **kn)
         elif fused:
             self.transmit(dsym, B, dcap, capture_len, n_blocks, dpre, pre_stride, taps=dtaps, n_taps=n_taps,
                           taps_stride=ts, cfo=dcfo, ow2=dow2, delay=ddelay, seed=seed, first_frame=first_frame)
         else:
-            dwave = DeviceArray((B, S), zero=True)
-            keep.append(dwave)
-            self.modulate(dsym, B, dwave, n_blocks, dpre, pre_stride)
-            self.channel(dwave, B, S, dcap, capture_len, dtaps, n_taps, ts, dpre is not None, dcfo, dow2, ddelay,
+            dwave, W = wave()
+            self.channel(dwave, B, W, dcap, capture_len, dtaps, n_taps, ts, dpre is not None, dcfo, dow2, ddelay,
                          seed, first_frame)
         return dcap, keep
 
     def transmit_host(self, sym, tx_pre=None, taps=None, cfo=None, ow2=None, delay=None, capture_len=None,
-                      seed=0x80211, first_frame=0, fused=True, knot_period=None):
+                      seed=0x80211, first_frame=0, fused=True, stf=False, knot_period=None):
         """Convenience: host symbols sym [B][n_blocks][53] (n_blocks 0..15) and, optionally, the preamble's 53
         bins tx_pre ([53] shared, or [B][53]) -> raw capture windows [B][capture_len] on the host.  taps [n_taps]
         or [B][n_taps] complex (None: a unit tap); cfo (cycles per sample), ow2 (noise variance per complex
@@ -860,7 +892,10 @@ class Context:
         length plus the taps' tail.  fused: one transmit launch, else modulate then channel -- the same bits.
         Taps that move within the packet (transmit_tv; fading_taps draws them): [B][K][n_taps], K knots
         knot_period samples apart (None: 80, a knot per block boundary, K = 19 for a full packet), or one shared
-        trajectory [K][n_taps], which needs knot_period given: without it 2-D taps are [B][n_taps]."""
+        trajectory [K][n_taps], which needs knot_period given: without it 2-D taps are [B][n_taps].
+        stf: 802.11a's short training field (short_field, at the rms of the context's non-zero tx preamble bins)
+        goes in front of the long one, which tx_pre must then provide: 160 samples more, built unfused; the
+        channel's time origin stays at the end of the first 160 samples."""
         sym = _as_c128(sym)
         if sym.ndim != 3 or sym.shape[2] != NSC or sym.shape[1] > NBLK:
             raise ValueError("sym must be [B][n_blocks <= 15][53] complex")
@@ -874,15 +909,15 @@ class Context:
         dsym = DeviceArray.from_numpy(sym) if n_blocks else None
         if capture_len is None:
             capture_len = (160 if dpre is not None else 0) + SAMPLES_PER_BLOCK * n_blocks + \
-                (np.shape(taps)[-1] if taps is not None else 1) - 1
+                (np.shape(taps)[-1] if taps is not None else 1) - 1 + (STF_LEN if stf else 0)
         dcap, keep = self._transmit_device(dsym, B, n_blocks, dpre, ps, taps, cfo, ow2, delay, int(capture_len), seed,
-                                           first_frame, fused, knot_period)
+                                           first_frame, fused, knot_period, stf)
         synchronize()
         return dcap.numpy()
 
     def link_host(self, modulation, rate, snr_db, n_frames, sources=(LT_LS, PS_LINEAR, PS_MMSE), taps=None, cfo=None,
                   delay=None, capture_len=1488, threshold=0.25, backoff=0, seed=0x80211, dd_iterations=0,
-                  scale=8.8753, knot_period=80, tracker=None):
+                  scale=8.8753, stf=False, stf_threshold=0.25, knot_period=80, tracker=None):
         """The experiment WiFi_RX.m:4-9 announces (SNR, channel_model, FO), for a batch, scored in coded bit
         errors: n_frames packets of random information bits (drawn on the host from `seed`, the last six 0) are
         re-encoded to symbols with 802.11's pilots, transmitted behind the context's tx preamble through `taps`
@@ -902,6 +937,12 @@ class Context:
         knot_period samples apart, through transmit_tv.  tracker (mu, beta): each source's estimate additionally
         starts a track_demodulate (no blend, phase tracking on) on the same capture, followed by
         soft_demap_blocks on its h_blocks and viterbi_decode; not together with dd_iterations.
+        stf: the packet carries 802.11a's short training field in front of the long one (1,520 samples; the
+        waveform is built unfused, and 3-D taps need knots that cover them) and the receiver runs
+        front_end_sync_stf (thresholds stf_threshold and threshold), which detects at any carrier offset and
+        estimates |cfo| < 1/32 cycles per sample, then the field and the blocks at its start and offset; the
+        result gains "metric_stf", and "metric" is the long field's.  capture_len must hold the packet,
+        1520 + n_taps - 1 + the largest delay samples (1,648 is a window with room for 128 more), else ValueError.
         -> {source: nbiterr uint32 [B]} plus "start" int32 [B] (-1: not detected; its counts are those of an
         all-zero decode), "metric" [B], "cfo" [B] (the estimate), "ow2" [B] and "bits" uint8 [B][T]; with
         tracker, "tracked": {source: nbiterr uint32 [B]} of the tracked runs."""
@@ -916,6 +957,11 @@ class Context:
         sources = tuple(sources)
         if not sources or any(s not in names for s in sources):
             raise ValueError("sources must be estimator bits")
+        if stf:
+            need = 1520 + (np.shape(taps)[-1] if taps is not None else 1) - 1 + \
+                (int(np.max(delay)) if delay is not None else 0)
+            if capture_len < need:
+                raise ValueError(f"capture_len {capture_len} cannot hold a packet with a short field: {need} samples")
         rng = np.random.default_rng(seed)
         bits = rng.integers(0, 2, (B, T), dtype=np.uint8)
         bits[:, T - 6:] = 0
@@ -928,12 +974,18 @@ class Context:
         self.reencode(dbits, B, modulation, rate, scale, tx=dtx)
         self.modulate(None, 1, dfield, 0, dpre)
         dcap, keep = self._transmit_device(dtx, B, NBLK, dpre, 0, taps, cfo, ow2, delay, int(capture_len), seed, 0,
-                                           True, knot_period if np.ndim(taps) == 3 else None)
+                                           True, knot_period if np.ndim(taps) == 3 else None, stf)
         dstart, dmetric = DeviceArray((B,), np.int32, zero=True), DeviceArray((B,), np.float64, zero=True)
         dow2e, dcfo = DeviceArray((B,), np.float64, zero=True), DeviceArray((B,), np.float64, zero=True)
         drx, drxpre = DeviceArray((B, NBLK, NSC), zero=True), DeviceArray((B, NSC), zero=True)
-        self.front_end_sync(dcap, B, capture_len, dfield.addr + 32 * 16, threshold, backoff, dstart, dmetric)
-        self.front_end_preamble(dcap, B, capture_len, drxpre, dow2e, cfo=dcfo, start=dstart)
+        if stf:
+            dmstf = DeviceArray((B,), np.float64, zero=True)
+            self.front_end_sync_stf(dcap, B, capture_len, dfield.addr + 32 * 16, stf_threshold, threshold, backoff,
+                                    dstart, dcfo, dmstf, dmetric)
+            self.front_end_preamble(dcap, B, capture_len, drxpre, dow2e, cfo=dcfo, estimate_cfo=False, start=dstart)
+        else:
+            self.front_end_sync(dcap, B, capture_len, dfield.addr + 32 * 16, threshold, backoff, dstart, dmetric)
+            self.front_end_preamble(dcap, B, capture_len, drxpre, dow2e, cfo=dcfo, start=dstart)
         self.front_end_blocks(dcap, B, NBLK, drx, cfo=dcfo, start=dstart, capture_len=capture_len)
         mask = LT_LS
         for s in sources:
@@ -966,6 +1018,8 @@ class Context:
         if tracker is not None:
             res["tracked"] = {s: dec["nbiterr"].numpy() for s, (trk, dec) in tracked.items()}
         res.update(start=dstart.numpy(), metric=dmetric.numpy(), cfo=dcfo.numpy(), ow2=ow2, bits=bits)
+        if stf:
+            res["metric_stf"] = dmstf.numpy()
         return res
 
     def _dd_device(self, fr, B, dbits, dtheta, modulation, rate, scale, terminated, dref, rounds):
@@ -1094,6 +1148,20 @@ class Context:
         _check(_lib.wce_front_end_sync(self.handle, _addr(capture), cs, capture_len, n_frames, _addr(ltf),
                                        threshold, backoff, _addr(start), _addr(metric), stream),
                "wce_front_end_sync")
+
+    def front_end_sync_stf(self, capture, n_frames, capture_len, ltf, threshold_stf, threshold_ltf, backoff=0,
+                           start=None, cfo=None, metric_stf=None, metric_ltf=None, capture_stride=None, stream=None):
+        """wce_front_end_sync_stf: detection on the short training field at any carrier offset, the coarse offset
+        from its lag-16 autocorrelation, front_end_sync's timing against ltf turned by it, and the two-copy fine
+        offset unwrapped by the coarse one, on raw capture windows (device) [n_frames][capture_stride].  start
+        (device int32 [n_frames]) as front_end_sync's; cfo (device float64 [n_frames]) the total offset in
+        cycles per sample, |e| < 1/32, NaN where start is -1 -- to be read by front_end_preamble(start=, cfo=,
+        estimate_cfo=False) and front_end_blocks(start=, cfo=).  metric_stf, metric_ltf (device float64
+        [n_frames], optional): the two metrics in [0, 1]."""
+        cs = capture_stride if capture_stride is not None else capture_len
+        _check(_lib.wce_front_end_sync_stf(self.handle, _addr(capture), cs, capture_len, n_frames, _addr(ltf),
+                                           threshold_stf, threshold_ltf, backoff, _addr(start), _addr(cfo),
+                                           _addr(metric_stf), _addr(metric_ltf), stream), "wce_front_end_sync_stf")
 
     def front_end_blocks(self, samples, n_frames, n_blocks=NBLK, sym=None, packet_stride=None,
                          frame_stride=NBLK * NSC, block_stride=NSC, stream=None, cfo=None, sample_offset=0,
@@ -1353,8 +1421,8 @@ class Context:
 
     def receive_capture_host(self, tx_packets, tx_lptot, rx_capture, threshold, backoff=0, mask=ALL,
                              semantics=SEM_MATLAB, cfo=False, sample_offset=0, demod_source=None,
-                             modulation=MOD_BPSK, scale=8.8753, track=True, decode_rate=None, ref_bits=None,
-                             terminated=True):
+                             modulation=MOD_BPSK, scale=8.8753, track=True, stf=False, stf_threshold=0.25,
+                             decode_rate=None, ref_bits=None, terminated=True):
         """receive_host with the rx side taken from raw capture windows [B][capture_len], in which each packet
         (long training field, then sample_offset samples, then the packet) starts at an unknown sample:
         front_end_sync against tx_lptot[0][-64:] finds each window's start (start - backoff, or -1 where the
@@ -1363,7 +1431,11 @@ class Context:
         window without a detected packet, or one the packet does not fit in, gives NaN rows.
         demod_source, modulation, scale, track: as receive_host; such a window's "demod" has NaN evm and
         0xFF symbols.  decode_rate, ref_bits, terminated: as receive_host; such a window's "decode" has
-        all-zero soft bits and all-zero bits."""
+        all-zero soft bits and all-zero bits.
+        stf: the windows' packets carry a short training field (transmit_host(stf=True)): front_end_sync_stf
+        (thresholds stf_threshold and threshold) finds start and the carrier offset, |cfo| < 1/32 cycles per
+        sample, which is removed whatever `cfo` says; the dict gains "cfo" and "metric_stf", and "metric" is
+        the long field's."""
         dem = self._demod_request(demod_source, mask, modulation, scale, track)
         dcd = self._decode_request(decode_rate, dem, ref_bits, terminated)
         pk, lp, cap = _as_c128(tx_packets), _as_c128(tx_lptot), _as_c128(rx_capture)
@@ -1378,22 +1450,29 @@ class Context:
         dltf = DeviceArray.from_numpy(np.ascontiguousarray(lp[0, -FFT_SIZE:]))
         dstart, dmetric = DeviceArray((B,), np.int32, zero=True), DeviceArray((B,), np.float64, zero=True)
         dow2 = DeviceArray((B,), np.float64, zero=True)
-        dcfo = DeviceArray((B,), np.float64, zero=True) if cfo else None
+        dcfo = DeviceArray((B,), np.float64, zero=True) if (cfo or stf) else None
         sym = [DeviceArray((B, NBLK, NSC), zero=True) for _ in (0, 1)]
         pre = [DeviceArray((B, NSC), zero=True) for _ in (0, 1)]
         self.front_end_blocks(dpk, B, NBLK, sym[0], packet_stride=pk.shape[1])
         self.front_end_preamble(dlp, B, lp.shape[1], pre[0], None)
         # same (null) stream throughout: each call reads what the one before wrote
-        self.front_end_sync(dcap, B, W, dltf, threshold, backoff, dstart, dmetric)
-        self.front_end_preamble(dcap, B, W, pre[1], dow2, cfo=dcfo, start=dstart)
+        if stf:
+            dmstf = DeviceArray((B,), np.float64, zero=True)
+            self.front_end_sync_stf(dcap, B, W, dltf, stf_threshold, threshold, backoff, dstart, dcfo, dmstf, dmetric)
+            self.front_end_preamble(dcap, B, W, pre[1], dow2, cfo=dcfo, estimate_cfo=False, start=dstart)
+        else:
+            self.front_end_sync(dcap, B, W, dltf, threshold, backoff, dstart, dmetric)
+            self.front_end_preamble(dcap, B, W, pre[1], dow2, cfo=dcfo, start=dstart)
         self.front_end_blocks(dcap, B, NBLK, sym[1], cfo=dcfo, sample_offset=sample_offset, start=dstart,
                               capture_len=W)
         res = self._estimate_device(sym[0], sym[1], pre[1], B, mask | FRAME_COV, 0, PS_LINEAR, semantics, pre[0],
                                     False, dow2, dem, dcd)
         res["ow2"] = dow2.numpy()
-        if cfo:
+        if cfo or stf:
             res["cfo"] = dcfo.numpy()
         res["start"], res["metric"] = dstart.numpy(), dmetric.numpy()
+        if stf:
+            res["metric_stf"] = dmstf.numpy()
         return res
 
 

@@ -412,6 +412,80 @@ int wce_front_end_blocks_at(wce_ctx *ctx, const wce_complex *capture, int64_t ca
                             int64_t sample_offset, wce_complex *sym, int64_t frame_stride, int64_t block_stride,
                             void *stream);
 
+/* ---- short training field: detection at any carrier offset, coarse offset ----
+ * wce_front_end_sync's metric loses sinc^2(64 e) to an offset of e cycles per
+ * sample and the two-copy estimate is unambiguous only for |e| < 1/128 (78 kHz
+ * at 10 MHz), a third of what 802.11p's +-20 ppm at each end of a 5.9 GHz link
+ * allow.  The short training field (STF), ten repetitions of a 16-sample period
+ * in front of the long field, carries a receiver over the rest: a lag-16
+ * autocorrelation detects it whatever the offset (which only turns the
+ * correlation's phase), that phase gives the offset within +-1/32 cycles per
+ * sample, and the long field gives timing and the fine offset once the coarse
+ * one is removed.
+ *
+ * wce_short_field is the transmitter's: wave[f*wave_stride + m] = amplitude *
+ * t[m mod 16] for m < 160, nothing else written.  t is the 64-point MATLAB ifft
+ * (1/64) of 802.11a's short sequence S = sqrt(13/6) (1 + j) s_k on the bins
+ * k = -24, -20 .. 24 without DC, signs {+ - + - - + - - + + + +}, placed by the
+ * library's bin map Y[(i - 26) mod 64] = S[i].  At amplitude 1 its mean sample
+ * power is 52/4096, the long field's for unit bins.  The 16 values of t are
+ * computed once on the host in 80-bit arithmetic and rounded to double; the
+ * kernel replicates them, so samples m and m + 16 of a row are the same bits.
+ * A packet with an STF is assembled from three calls: wce_short_field writes
+ * wave[0..160), wce_modulate writes from wave + 160, and wce_channel /
+ * wce_channel_tv runs with wave_len = 1520 and field = 1.  The channel's time
+ * origin then sits 160 samples early: one common phase exp(2 pi i cfo 160) on
+ * field and data alike, which the estimators absorb.  wce_transmit sends no STF.
+ * WCE_EINVAL: NULL ctx or wave; wave not 16-byte aligned; wave_stride < 160; a
+ * non-finite amplitude; n_frames < 0.  n_frames == 0 is WCE_OK.
+ *
+ * wce_front_end_sync_stf, per window x[0..L), L = capture_len, every frame on its
+ * own:
+ *  1. Detection.  For 0 <= d <= L - 144
+ *         P[d] = sum_{n<128} x[d+n+16] conj(x[d+n])
+ *         A[d] = sum_{n<128} |x[d+n]|^2,  B[d] = sum_{n<128} |x[d+n+16]|^2
+ *     d_s is the smallest d attaining max |P[d]|^2 and Ms = |P[d_s]|^2 /
+ *     (A[d_s] B[d_s]), 0 where the denominator is 0; Ms is in [0, 1] by
+ *     Cauchy-Schwarz.  The maximum is taken un-normalised on purpose: in a
+ *     noise-free capture the normalised ratio is 1 as soon as the window touches
+ *     the STF.
+ *  2. Coarse offset.  e_c = arg P[d_s] / (2 pi 16).
+ *  3. Timing.  wce_front_end_sync's metric with the template turned by e_c,
+ *         c[d] = sum_{n<64} x[d+n] conj(ltf[n] exp(2 pi i e_c n)),
+ *     E[d], El, M[d] = 2 |c[d]| |c[d+64]| / (El E[d]) over 0 <= d <= L - 128 as
+ *     there; d* is the smallest d attaining max M and Ml = M[d*].  (The device
+ *     derotates the samples as it stages them, with an exactly reduced phase: the
+ *     same moduli up to rounding.)
+ *  4. Start.  s = d* - backoff.  The frame is detected iff Ms >= threshold_stf,
+ *     Ml >= threshold_ltf and s >= 0; then start[f] = s, with
+ *     wce_front_end_sync's meaning, and feeds the _at calls unchanged.
+ *     Otherwise start[f] = -1 and cfo[f] = NaN.
+ *  5. Fine offset, unwrapped.  For a detected frame
+ *         e_f = arg(sum_{n<64} x[s+64+n] conj(x[s+n])) / (2 pi 64),
+ *     the _at call's two-copy estimate on the same samples, and
+ *         cfo[f] = e_f + rint((e_c - e_f) 64) / 64,
+ *     to be given to wce_front_end_preamble_at (estimate = 0) and
+ *     wce_front_end_blocks_at.  The total range is |e| < 1/32.
+ *  - metric_stf[f] = Ms and metric_ltf[f] = Ml (either pointer may be NULL),
+ *    written whether or not the frame is detected.
+ *  - A window holding a non-finite sample, or a non-finite ltf, gives start -1
+ *    and NaN in cfo and both metrics: a sample marks its own frame only, the ltf
+ *    is shared and marks every frame.
+ *  - A frame's bits depend only on its own window and the arguments; nothing is
+ *    read outside [0, L); nothing is read back or allocated, and the call is
+ *    asynchronous on stream.
+ *  - WCE_EINVAL before any launch: capture_len < 144 or >= 2^31; capture_stride <
+ *    capture_len; either threshold outside [0, 1] or not finite; backoff outside
+ *    [0, 31]; start or cfo NULL or not 4-byte / 8-byte aligned; a metric pointer
+ *    not 8-byte aligned; ltf or capture NULL or not 16-byte aligned; n_frames < 0.
+ *    n_frames == 0 is WCE_OK. */
+int wce_short_field(wce_ctx *ctx, double amplitude, wce_complex *wave, int64_t wave_stride, int64_t n_frames,
+                    void *stream);
+int wce_front_end_sync_stf(wce_ctx *ctx, const wce_complex *capture, int64_t capture_stride, int64_t capture_len,
+                           int64_t n_frames, const wce_complex *ltf, double threshold_stf, double threshold_ltf,
+                           int32_t backoff, int32_t *start, double *cfo, double *metric_stf, double *metric_ltf,
+                           void *stream);
+
 /* ---- demodulation: pilot phase tracking, slicer, EVM (the reference's README
  * applies the estimate "before the symbols are decoded"; WiFi_Equalization.m
  * stops at the equalized symbols) ----

@@ -88,7 +88,7 @@ int wce_debug_set_flat_chunk(long long frames);
  * workgroups, so that a few dozen frames make every wave take several trips
  * round its frame loop, the last one ragged).  Read by the launchers whose
  * kernels loop over frames: the front end's six builds, wce_front_end_sync,
- * wce_demodulate without evm and nerr, wce_soft_demap and _blocks,
+ * wce_front_end_sync_stf, wce_short_field, wce_demodulate without evm and nerr, wce_soft_demap and _blocks,
  * wce_viterbi_decode, wce_reencode, wce_modulate, wce_channel, wce_transmit.
  * A frame's outputs depend on its own data alone, so 1 gives the bits of 0.
  * Ignored by wce_demodulate with evm or nerr and by wce_track_demodulate:
@@ -100,6 +100,13 @@ int wce_debug_set_variant(int which, int value);
  * own cap and the current which 6: min(blocks, own_cap), or min(blocks, 3) with
  * the knob set.  Needs no device. */
 long long wce_debug_chain_grid(long long blocks, long long own_cap);
+/* One period of wce_short_field's field at amplitude 1: 16 {re, im} pairs, as the call passes them to its
+ * kernel.  Needs no device. */
+int wce_debug_short_field_period(double *out);
+/* The lags one tile of wce_front_end_sync_stf's kernel covers in its first (STF) and second (LTF) pass: a window
+ * takes another tile of the first pass when capture_len - 144 reaches a multiple of *lags_stf, of the second
+ * when capture_len - 128 reaches a multiple of *lags_ltf.  Needs no device. */
+int wce_debug_sync_stf_tiles(int *lags_stf, int *lags_ltf);
 /* (frame, block) units one sweep of mmse_rank1_kernel's persistent grid
  * (which 5 = 7) covers on ctx's device: 16 per workgroup times the workgroups
  * resident at once (4 per CU, the CU count read when ctx was made).  A larger
