@@ -13,6 +13,7 @@ from .wce import (  # noqa: F401
     DEC_TERMINATED, RATE_1_2, RATE_2_3, RATE_3_4, info_bits, ReencodePar, ReencodeOut,
     ChannelPar, FadingPar, pdp_taps, fading_taps,
     TRACK_KNOWN_TX, TRACK_PHASE, TRACK_REF_TX, Track, TrackOut,
+    COMBINE_MAX_BRANCHES, CombinePar, CombineOut,
 )
 
 __version__ = "0.1.0"

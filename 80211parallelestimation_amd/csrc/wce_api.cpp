@@ -1203,6 +1203,98 @@ int wce_track_demodulate(wce_ctx *c, const wce_frames *in, const wce_track *p, c
     return rc ? fail(rc, "track launch") : WCE_OK;
 }
 
+// ---------------------------------------------------------------- receive diversity
+static bool strides_hold(int64_t n, int64_t fs, int64_t bs, int64_t row);
+
+// A branches of stride s on top of frames [n][15][53] of strides fs / bs: no two branches share an element where
+// the branch stride spans a whole branch, or fits the branches inside a block stride, or between frame and block.
+// 128-bit products: the strides are the caller's
+static bool branches_apart(int64_t A, int64_t s, int64_t n, int64_t fs, int64_t bs)
+{
+    typedef __int128 i128;
+    if (A <= 1) return true;
+    if (s < wce::NSC) return false;
+    const i128 blocks = (i128)(wce::NBLK - 1) * bs + wce::NSC, all = (i128)(A - 1) * s;
+    if ((i128)s >= (i128)(n > 1 ? n - 1 : 0) * fs + blocks) return true;
+    if (all + wce::NSC <= (i128)bs) return true;
+    return (i128)s >= blocks && all + blocks <= (i128)fs;
+}
+// the same for rows [n][53] of stride hs
+static bool rows_apart(int64_t A, int64_t s, int64_t n, int64_t hs)
+{
+    typedef __int128 i128;
+    if (A <= 1) return true;
+    if (s < wce::NSC) return false;
+    if ((i128)s >= (i128)(n > 1 ? n - 1 : 0) * hs + wce::NSC) return true;
+    return (i128)(A - 1) * s + wce::NSC <= (i128)hs;
+}
+
+int wce_combine(wce_ctx *c, const wce_combine_par *p, int64_t n_frames, const wce_combine_out *out, void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    if (!p || !out) return fail(WCE_EINVAL, "wce_combine: null parameters or outputs");
+    if (!p->rx || !p->h) return fail(WCE_EINVAL, "wce_combine: rx and h required");
+    if (!out->rx && !out->h) return fail(WCE_EINVAL, "wce_combine: no output requested");
+    const int64_t A = p->n_branches, n = n_frames;
+    if (A < 1 || A > WCE_COMBINE_MAX_BRANCHES) return fail(WCE_EINVAL, "wce_combine: n_branches outside 1..8");
+    if (n < 0 || n > 0x7fffffffll) return fail(WCE_EINVAL, "wce_combine: n_frames < 0 or > 2^31 - 1");
+    if (!strides_hold(n, p->rx_frame_stride, p->rx_block_stride, wce::NSC))
+        return fail(WCE_EINVAL, "wce_combine: rx strides too small");
+    if (p->h_stride < wce::NSC) return fail(WCE_EINVAL, "wce_combine: h_stride < 53");
+    if (out->rx && !strides_hold(n, out->rx_frame_stride, out->rx_block_stride, wce::NSC))
+        return fail(WCE_EINVAL, "wce_combine: output rx strides too small");
+    if (out->h && out->h_stride < wce::NSC) return fail(WCE_EINVAL, "wce_combine: output h_stride < 53");
+    if (!branches_apart(A, p->rx_branch_stride, n, p->rx_frame_stride, p->rx_block_stride))
+        return fail(WCE_EINVAL, "wce_combine: rx_branch_stride makes branches overlap");
+    if (!rows_apart(A, p->h_branch_stride, n, p->h_stride))
+        return fail(WCE_EINVAL, "wce_combine: h_branch_stride makes branches overlap");
+    if (p->ow2 && A > 1 && p->ow2_branch_stride < n)
+        return fail(WCE_EINVAL, "wce_combine: ow2_branch_stride < n_frames");
+    if (reinterpret_cast<uintptr_t>(p->rx) % 16 || reinterpret_cast<uintptr_t>(p->h) % 16 ||
+        reinterpret_cast<uintptr_t>(out->rx) % 16 || reinterpret_cast<uintptr_t>(out->h) % 16)
+        return fail(WCE_EINVAL, "wce_combine: rx, h or an output not 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(p->ow2) % 8) return fail(WCE_EINVAL, "wce_combine: ow2 not 8-byte aligned");
+    if (n == 0) return WCE_OK;
+    wce::CombineArgs a{};
+    a.rx = reinterpret_cast<const double *>(p->rx);
+    a.h = reinterpret_cast<const double *>(p->h);
+    a.ow2 = p->ow2;
+    a.rbs = A > 1 ? p->rx_branch_stride : 0; a.rfs = p->rx_frame_stride; a.rks = p->rx_block_stride;
+    a.hbs = A > 1 ? p->h_branch_stride : 0; a.hs = p->h_stride;
+    a.obs = A > 1 ? p->ow2_branch_stride : 0; a.n = n; a.na = (int32_t)A;
+    a.orx = reinterpret_cast<double *>(out->rx);
+    a.ofs = out->rx_frame_stride; a.oks = out->rx_block_stride;
+    a.oh = reinterpret_cast<double *>(out->h);
+    a.ohs = out->h_stride;
+    DeviceGuard g(c->device);
+    const int rc = wce::launch_combine(a, stream);
+    return rc ? fail(rc, "combine launch") : WCE_OK;
+}
+
+int wce_sync_share(wce_ctx *c, int32_t n_branches, int64_t branch_stride, int64_t n_packets, const double *metric,
+                   int32_t *start, double *cfo, void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    if (!metric || reinterpret_cast<uintptr_t>(metric) % 8)
+        return fail(WCE_EINVAL, "wce_sync_share: metric null or not 8-byte aligned");
+    if (!start && !cfo) return fail(WCE_EINVAL, "wce_sync_share: start and cfo both null");
+    if (reinterpret_cast<uintptr_t>(start) % 4) return fail(WCE_EINVAL, "wce_sync_share: start not 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(cfo) % 8) return fail(WCE_EINVAL, "wce_sync_share: cfo not 8-byte aligned");
+    if (n_branches < 1 || n_branches > WCE_COMBINE_MAX_BRANCHES)
+        return fail(WCE_EINVAL, "wce_sync_share: n_branches outside 1..8");
+    if (n_packets < 0 || n_packets > 0x7fffffffll)
+        return fail(WCE_EINVAL, "wce_sync_share: n_packets < 0 or > 2^31 - 1");
+    if (n_branches > 1 && branch_stride < n_packets)
+        return fail(WCE_EINVAL, "wce_sync_share: branch_stride < n_packets");
+    if (n_packets == 0) return WCE_OK;
+    wce::SyncShareArgs a{};
+    a.metric = metric; a.start = start; a.cfo = cfo;
+    a.bs = n_branches > 1 ? branch_stride : 0; a.n = n_packets; a.na = n_branches;
+    DeviceGuard g(c->device);
+    const int rc = wce::launch_sync_share(a, stream);
+    return rc ? fail(rc, "sync_share launch") : WCE_OK;
+}
+
 // ---------------------------------------------------------------- decoding
 int wce_decode_info_bits(int32_t modulation, int32_t rate)
 {

@@ -351,6 +351,29 @@ struct TxTvArgs {
     TxKnots k;
 };
 
+// maximal-ratio combining (wce_combine.hip): branch q of packet f is rx[q*rbs + f*rfs + b*rks + k],
+// h[q*hbs + f*hs + k] and ow2[q*obs + f] (ow2 null: every weight 1)
+struct CombineArgs {
+    const double *rx, *h, *ow2;
+    int64_t rbs, rfs, rks, hbs, hs, obs, n;
+    int32_t na;           // branches, 1 .. WCE_COMBINE_MAX_BRANCHES
+    double *orx;          // orx[f*ofs + b*oks + k]; each output may be null, not both
+    int64_t ofs, oks;
+    double *oh;           // oh[f*ohs + k]
+    int64_t ohs;
+};
+
+// the antennas' shared timing (wce_combine.hip): entry q*bs + p is branch q of packet p
+struct SyncShareArgs {
+    const double *metric;
+    int32_t *start;       // each may be null, not both
+    double *cfo;
+    int64_t bs, n;
+    int32_t na;
+};
+
+int launch_combine(const CombineArgs &a, void *stream);
+int launch_sync_share(const SyncShareArgs &a, void *stream);
 int launch_modulate(const TxArgs &a, void *stream);
 int launch_channel(const TxArgs &a, void *stream);
 int launch_transmit(const TxArgs &a, void *stream);
@@ -493,7 +516,8 @@ constexpr int WCE_VARIANT_R1 = 5;      // PS_MMSE with a rank-1 covariance (TEXT
 constexpr int WCE_VARIANT_GRID = 6;    // the receive and transmit chain's looping launchers (launch_front, launch_sync,
                                       // launch_sync_stf, launch_short_field,
                                       // launch_demod's builds without evm / nerr, launch_demap, launch_viterbi,
-                                      // launch_reencode, the three transmit launches): 0 = each its own grid cap
+                                      // launch_reencode, the three transmit launches, launch_combine,
+                                      // launch_sync_share): 0 = each its own grid cap
                                       // (default), else at most CHAIN_TEST_GRID workgroups, so that a few dozen frames
                                       // make every wave loop over several, the last trip ragged.  A test seam, not an
                                       // A/B: a frame's outputs depend on its own data alone, so the bits are those of 0.

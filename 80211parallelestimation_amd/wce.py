@@ -44,6 +44,7 @@ STF_LEN = 160            # short training field: ten periods of 16 samples (wce_
 SEM_C = 0          # main.c semantics
 SEM_MATLAB = 1     # WiFi_channel_estimation_*.m semantics
 MOD_BPSK, MOD_QPSK, MOD_QAM16, MOD_QAM64 = 1, 2, 4, 6   # wce_demod.modulation: bits per data symbol
+COMBINE_MAX_BRANCHES = 8   # WCE_COMBINE_MAX_BRANCHES: antennas wce_combine and wce_sync_share take
 DEMOD_TRACK = 1 << 0     # remove each block's common pilot phase
 DEMOD_REF_TX = 1 << 1    # EVM against tx instead of the decided point
 TRACK_PHASE = 1 << 0     # WCE_TRACK_PHASE: per-block common pilot phase, as DEMOD_TRACK
@@ -116,6 +117,19 @@ class TrackOut(ctypes.Structure):
                 ("eq_frame_stride", c_int64), ("eq_block_stride", c_int64), ("sym_frame_stride", c_int64),
                 ("sym_block_stride", c_int64), ("h_blocks", c_void_p), ("hb_frame_stride", c_int64),
                 ("hb_block_stride", c_int64), ("h_last", c_void_p), ("h_last_stride", c_int64)]
+
+
+class CombinePar(ctypes.Structure):
+    """struct wce_combine_par (include/wce.h)."""
+    _fields_ = [("rx", c_void_p), ("rx_branch_stride", c_int64), ("rx_frame_stride", c_int64),
+                ("rx_block_stride", c_int64), ("h", c_void_p), ("h_branch_stride", c_int64), ("h_stride", c_int64),
+                ("ow2", c_void_p), ("ow2_branch_stride", c_int64), ("n_branches", c_int32)]
+
+
+class CombineOut(ctypes.Structure):
+    """struct wce_combine_out (include/wce.h)."""
+    _fields_ = [("rx", c_void_p), ("rx_frame_stride", c_int64), ("rx_block_stride", c_int64), ("h", c_void_p),
+                ("h_stride", c_int64)]
 
 
 class ReencodePar(ctypes.Structure):
@@ -210,6 +224,8 @@ ABI = {
                                 c_void_p, c_int64, c_int64, c_void_p],
     "wce_demodulate": [c_void_p, POINTER(Frames), POINTER(Demod), POINTER(DemodOut), c_void_p],
     "wce_track_demodulate": [c_void_p, POINTER(Frames), POINTER(Track), POINTER(TrackOut), c_void_p],
+    "wce_combine": [c_void_p, POINTER(CombinePar), c_int64, POINTER(CombineOut), c_void_p],
+    "wce_sync_share": [c_void_p, c_int32, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
     "wce_soft_demap_blocks": [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_double,
                               c_int64, c_void_p, c_int64, c_int64, c_void_p],
     "wce_soft_demap": [c_void_p, c_void_p, c_int64, c_int64, POINTER(Demod), c_int64, c_void_p, c_int64, c_int64,
@@ -1020,6 +1036,187 @@ class Context:
         res.update(start=dstart.numpy(), metric=dmetric.numpy(), cfo=dcfo.numpy(), ow2=ow2, bits=bits)
         if stf:
             res["metric_stf"] = dmstf.numpy()
+        return res
+
+    def combine(self, rx, h, n_frames, n_branches, ow2=None, out_rx=None, out_h=None, rx_branch_stride=None,
+                rx_frame_stride=None, rx_block_stride=NSC, h_branch_stride=None, h_stride=NSC,
+                ow2_branch_stride=None, out_frame_stride=None, out_block_stride=NSC, out_h_stride=NSC, stream=None):
+        """wce_combine on device arrays: maximal-ratio combining of n_branches antenna branches of n_frames
+        packets.  rx complex [A][n][15][53], h complex [A][n][53] (any estimate) and, optionally, ow2 float64
+        [A][n] (each branch's noise variance: the weights become 1 / ow2 and the combined noise has unit variance;
+        None: unit weights) -> out_rx complex [n][15][53] and out_h complex [n][53] (real: sqrt of the summed
+        weighted |h|^2), each optional, laid out as every later call of the chain reads them.  A branch with a
+        non-finite h row or an ow2 that is not finite and positive is left out, bit for bit; a packet with none
+        left gets NaN rows.  The strides default to dense branch-major arrays (frame strides 15 block strides,
+        branch strides n frame strides); any layout whose branches do not overlap is taken."""
+        rfs = rx_frame_stride if rx_frame_stride is not None else NBLK * rx_block_stride
+        p = CombinePar(_addr(rx), rx_branch_stride if rx_branch_stride is not None else n_frames * rfs, rfs,
+                       rx_block_stride, _addr(h),
+                       h_branch_stride if h_branch_stride is not None else n_frames * h_stride, h_stride, _addr(ow2),
+                       ow2_branch_stride if ow2_branch_stride is not None else n_frames, n_branches)
+        o = CombineOut(_addr(out_rx), out_frame_stride if out_frame_stride is not None else NBLK * out_block_stride,
+                       out_block_stride, _addr(out_h), out_h_stride)
+        _check(_lib.wce_combine(self.handle, byref(p), n_frames, byref(o), stream), "wce_combine")
+
+    def sync_share(self, metric, n_packets, n_branches, start=None, cfo=None, branch_stride=None, stream=None):
+        """wce_sync_share on device arrays [A][branch_stride]: the antennas of a radio share one oscillator and one
+        packet arrival, so every branch of packet p takes the start (int32, front_end_sync's) and the offset cfo
+        (float64) of the branch that detected it with the largest metric (float64; the lowest branch on a tie), in
+        place.  A branch is live with start >= 0 and a finite metric; a packet with no live branch is left as it
+        is.  start None: the offset alone is shared (live: a finite metric); cfo None: the start alone."""
+        _check(_lib.wce_sync_share(self.handle, n_branches, branch_stride if branch_stride is not None else n_packets,
+                                   n_packets, _addr(metric), _addr(start), _addr(cfo), stream), "wce_sync_share")
+
+    def combine_host(self, rx, h, ow2=None):
+        """Convenience: host branches rx [A][B][15][53], estimates h [A][B][53] and, optionally, noise variances
+        ow2 [A][B] -> dict of host arrays rx [B][15][53] and h [B][53] (combine)."""
+        rx, h = _as_c128(rx), _as_c128(h)
+        if rx.ndim != 4 or rx.shape[2:] != (NBLK, NSC):
+            raise ValueError("rx must be [A][B][15][53] complex")
+        A, B = rx.shape[:2]
+        if h.shape != (A, B, NSC):
+            raise ValueError("h must be [A][B][53] complex")
+        dow2 = None
+        if ow2 is not None:
+            ow2 = np.ascontiguousarray(ow2, np.float64)
+            if ow2.shape != (A, B):
+                raise ValueError("ow2 must be [A][B]")
+            dow2 = DeviceArray.from_numpy(ow2)
+        drx, dh = DeviceArray.from_numpy(rx), DeviceArray.from_numpy(h)
+        d = {"rx": DeviceArray((B, NBLK, NSC), zero=True), "h": DeviceArray((B, NSC), zero=True)}
+        self.combine(drx, dh, B, A, dow2, d["rx"], d["h"])
+        synchronize()
+        return {n: a.numpy() for n, a in d.items()}
+
+    def link_mrc_host(self, modulation, rate, snr_db, n_frames, n_rx, taps, sources=(LT_LS, PS_LINEAR, PS_MMSE),
+                      branch_loss_db=None, share_sync=True, weighted=True, cfo=None, delay=None, capture_len=1488,
+                      threshold=0.25, backoff=0, seed=0x80211, dd_iterations=0, scale=8.8753, stf=False,
+                      stf_threshold=0.25, knot_period=80, tracker=None, keep_capture=False):
+        """link_host behind n_rx receive antennas: n_frames packets of random information bits (link_host's draw
+        from `seed`) are re-encoded once and transmitted once per branch on the same symbols, through that
+        branch's taps ([A][n_taps], or [A][B][n_taps]; with a knot axis, [A][B][K][n_taps], through transmit_tv)
+        with a shared carrier offset cfo and delay and the branch's own noise (first_frame = a B: nominal snr_db
+        as link_host, less branch_loss_db[a] dB, None: 0).  The receiver runs over all A B windows at once:
+        front_end_sync (front_end_sync_stf with stf), sync_share (share_sync: a branch in a fade takes the start
+        and the offset of the one that detected best), the _at front end, estimate, and per source (estimator
+        bits) combine -- weighted by each branch's estimated noise variance, the front end's ow2 (weighted), or
+        by 1 -- then demodulate (tracked phase, no blend), soft_demap and viterbi_decode on the combined stream;
+        dd_iterations and tracker (mu, beta) as link_host, on the combined stream.  Each branch alone goes through
+        link_host's own chain beside it.  Only bits go up and only error counts come down.
+        -> {source: {"combined": nbiterr uint32 [B], "branch": nbiterr uint32 [A][B]}}; with tracker, "tracked":
+        the same per source for the tracked runs; plus "start" int32, "metric", "cfo", "ow2" (the transmitter's)
+        and "ow2_est" (the front end's), each [A][B], after sharing, and "bits" uint8 [B][T]; with stf,
+        "metric_stf"; with keep_capture, "capture" complex [A][B][capture_len].  n_rx = 1 gives link_host's
+        counts as branch 0."""
+        A, B, T = int(n_rx), int(n_frames), info_bits(modulation, rate)
+        if not 1 <= A <= COMBINE_MAX_BRANCHES:
+            raise ValueError("n_rx must be 1..8")
+        if tracker is not None and dd_iterations:
+            raise ValueError("tracker with dd_iterations > 0 (decoder-in-the-loop tracking) is not built")
+        if tracker is not None:
+            mu, beta = tracker
+        if self.tx_pre is None:
+            raise ValueError("link_mrc_host needs a context built from a tx preamble")
+        names = {LT_LS: "lt_ls", PS_LINEAR: "ps_linear", PS_CUBIC: "ps_cubic", PS_SINC: "ps_sinc", PS_MMSE: "ps_mmse"}
+        sources = tuple(sources)
+        if not sources or any(s not in names for s in sources):
+            raise ValueError("sources must be estimator bits")
+        taps = _as_c128(taps)
+        if taps.ndim not in (2, 3, 4) or taps.shape[0] != A or (taps.ndim >= 3 and taps.shape[1] != B):
+            raise ValueError("taps must be [A][n_taps], [A][B][n_taps] or [A][B][K][n_taps] complex")
+        loss = np.zeros(A) if branch_loss_db is None else np.asarray(branch_loss_db, np.float64)
+        if loss.shape != (A,):
+            raise ValueError("branch_loss_db must be [A]")
+        if stf:
+            need = 1520 + taps.shape[-1] - 1 + (int(np.max(delay)) if delay is not None else 0)
+            if capture_len < need:
+                raise ValueError(f"capture_len {capture_len} cannot hold a packet with a short field: {need} samples")
+        N, L = A * B, int(capture_len)
+        rng = np.random.default_rng(seed)
+        bits = rng.integers(0, 2, (B, T), dtype=np.uint8)
+        bits[:, T - 6:] = 0
+        ow2 = np.ascontiguousarray(np.broadcast_to(
+            (52.0 * scale * scale / 4096.0) / 10.0 ** (np.asarray(snr_db, np.float64) / 10.0), (B,))[None] *
+            10.0 ** (loss / 10.0)[:, None])
+        all_bits = np.tile(bits, (A, 1))
+        dbits = DeviceArray.from_numpy(np.packbits(all_bits, axis=1, bitorder="little"))
+        dtx = DeviceArray((N, NBLK, NSC), zero=True)   # the same symbols once per branch: frame a B + f is packet f
+        dpre = DeviceArray.from_numpy(self.tx_pre)
+        dfield = DeviceArray((160,), zero=True)
+        self.reencode(dbits, N, modulation, rate, scale, tx=dtx)
+        self.modulate(None, 1, dfield, 0, dpre)
+        dcap = DeviceArray((N, L), zero=True)
+        keep = []
+        for a in range(A):
+            cap_a, k = self._transmit_device(dtx, B, NBLK, dpre, 0, taps[a], cfo, ow2[a], delay, L, seed, a * B, True,
+                                             knot_period if taps.ndim == 4 else None, stf)
+            _check(_lib.wce_memcpy_dtod(c_void_p(dcap.addr + a * B * L * 16), cap_a.ptr, B * L * 16, None),
+                   "wce_memcpy_dtod")
+            keep += [cap_a, k]
+        dow2 = DeviceArray.from_numpy(ow2)
+        dstart, dmetric = DeviceArray((N,), np.int32, zero=True), DeviceArray((N,), np.float64, zero=True)
+        dow2e, dcfo = DeviceArray((N,), np.float64, zero=True), DeviceArray((N,), np.float64, zero=True)
+        drx, drxpre = DeviceArray((N, NBLK, NSC), zero=True), DeviceArray((N, NSC), zero=True)
+        share = share_sync and A > 1
+        if stf:
+            dmstf = DeviceArray((N,), np.float64, zero=True)
+            self.front_end_sync_stf(dcap, N, L, dfield.addr + 32 * 16, stf_threshold, threshold, backoff, dstart, dcfo,
+                                    dmstf, dmetric)
+            if share:
+                self.sync_share(dmetric, B, A, dstart, dcfo)
+            self.front_end_preamble(dcap, N, L, drxpre, dow2e, cfo=dcfo, estimate_cfo=False, start=dstart)
+        else:
+            self.front_end_sync(dcap, N, L, dfield.addr + 32 * 16, threshold, backoff, dstart, dmetric)
+            if share:
+                self.sync_share(dmetric, B, A, dstart, None)
+            self.front_end_preamble(dcap, N, L, drxpre, dow2e, cfo=dcfo, start=dstart)
+            if share:   # one oscillator: the best branch's offset for all, and the fields again with it
+                self.sync_share(dmetric, B, A, None, dcfo)
+                self.front_end_preamble(dcap, N, L, drxpre, dow2e, cfo=dcfo, estimate_cfo=False, start=dstart)
+        self.front_end_blocks(dcap, N, NBLK, drx, cfo=dcfo, start=dstart, capture_len=L)
+        mask = LT_LS
+        for s in sources:
+            mask |= s
+        outs = {n: DeviceArray((N, NSC), zero=True) for bit, n in names.items() if mask & bit}
+        o = Outputs(*[(outs[n].addr if n in outs else None) for n in names.values()], None, NSC, NBLK * NSC, NSC,
+                    PS_LINEAR, 0)
+        fr = self.frames(dtx, drx, N, rx_pre=drxpre, tx_pre=dpre)
+        if mask & PS_MMSE and self.mode == MMSE_TEXTBOOK:
+            self.estimate(fr, o, mask | FRAME_COV, ow2=dow2)
+        else:
+            self.estimate(fr, o, mask)
+
+        def chains(frames, n, h, hlt, ref):   # link_host's runs on n frames -> (static or dd decode, tracked decode)
+            dem = self._demod_device(frames, n, h, hlt, modulation, scale, True, True)
+            dec = self._decode_device(dem["eq"], h, hlt, n, modulation, rate, scale, True, ref)
+            dd = self._dd_device(frames, n, dec["bits"], dem["theta"], modulation, rate, scale, True, dec["_ref"],
+                                 int(dd_iterations)) if dd_iterations else None
+            trk = tdec = None
+            if tracker is not None:
+                trk = self._track_device(frames, n, h, mu, beta, modulation, scale, True, True)
+                tdec = self._decode_device(trk["eq"], None, None, n, modulation, rate, scale, True, ref,
+                                           h_blocks=trk["h_blocks"])
+            return (dd if dd is not None else dec), tdec, (dem, dec, dd, trk)
+        runs = {}
+        for s in sources:
+            h = outs[names[s]]
+            alone = chains(fr, N, h, None if s == LT_LS else outs["lt_ls"], all_bits)
+            drxc, dhc = DeviceArray((B, NBLK, NSC), zero=True), DeviceArray((B, NSC), zero=True)
+            self.combine(drx, h, B, A, dow2e if weighted else None, drxc, dhc)
+            runs[s] = (alone, chains(self.frames(dtx, drxc, B), B, dhc, None, bits), drxc, dhc)
+        synchronize()
+        res = {s: {"combined": comb[0]["nbiterr"].numpy(), "branch": alone[0]["nbiterr"].numpy().reshape(A, B)}
+               for s, (alone, comb, _, _) in runs.items()}
+        if tracker is not None:
+            res["tracked"] = {s: {"combined": comb[1]["nbiterr"].numpy(),
+                                  "branch": alone[1]["nbiterr"].numpy().reshape(A, B)}
+                              for s, (alone, comb, _, _) in runs.items()}
+        res.update(start=dstart.numpy().reshape(A, B), metric=dmetric.numpy().reshape(A, B),
+                   cfo=dcfo.numpy().reshape(A, B), ow2=ow2, ow2_est=dow2e.numpy().reshape(A, B), bits=bits)
+        if stf:
+            res["metric_stf"] = dmstf.numpy().reshape(A, B)
+        if keep_capture:
+            res["capture"] = dcap.numpy().reshape(A, B, L)
         return res
 
     def _dd_device(self, fr, B, dbits, dtheta, modulation, rate, scale, terminated, dref, rounds):

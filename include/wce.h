@@ -914,6 +914,99 @@ int wce_transmit_tv(wce_ctx *ctx, const wce_complex *tx_pre, int64_t pre_stride,
                     const wce_fading_par *p, wce_complex *capture, int64_t capture_stride, int64_t capture_len,
                     void *stream);
 
+/* ---- receive diversity: maximal-ratio combining of antenna branches (the reference
+ * has one receive antenna; 802.11p radios ship with two, because a deep fade on one
+ * branch is what loses a packet) ----
+ * A radio with A antennas records A captures of each packet.  Every stage in front of
+ * the combiner runs on the A x B windows as on any batch: sync, the _at front end,
+ * wce_estimate / wce_estimate_noise over A x B frames.  wce_combine then folds the A
+ * branches of each packet into one received stream and one channel estimate with the
+ * layouts every later call reads, so wce_demodulate, wce_track_demodulate,
+ * wce_soft_demap(_blocks), wce_viterbi_decode and wce_reencode run on them unchanged.
+ *
+ * Branch a < A = n_branches of packet f < n_frames holds
+ *     rx_a[b][k] = rx[a*rx_branch_stride + f*rx_frame_stride + b*rx_block_stride + k],
+ *     h_a[k]     = h[a*h_branch_stride + f*h_stride + k]   any estimate (LT_LS, PS_MMSE, H_dd ...),
+ *     ow2_a      = ow2[a*ow2_branch_stride + f]             its noise variance, with ow2 != NULL.
+ * Branch-major arrays ([A][B]..., what one transmit call per branch with first_frame =
+ * a*B leaves) have branch strides that span a whole branch; a branch-minor layout (the
+ * branches of a block, or of a packet, next to each other) has a small one.  With
+ * V = {0..52} without 26 and v_a = 1 / ow2_a (1 when ow2 == NULL):
+ *     live(a)    every h_a[k], k in V, is finite, and (ow2 == NULL or ow2_a is finite and > 0)
+ *     g2[k]      = sum over live a, a ascending, of v_a |h_a[k]|^2,    g[k] = sqrt(g2[k])
+ *     rx_c[b][k] = (sum over live a, a ascending, of v_a conj(h_a[k]) rx_a[b][k]) / g[k]    k in V
+ *     h_c[k]     = g[k] + 0i                                                               k in V
+ *     rx_c[b][26] = 0, h_c[26] = 0; where g[k] == 0, rx_c[b][k] = 0 and h_c[k] = 0.
+ * out->rx[f*rx_frame_stride + b*rx_block_stride + k] = rx_c, out->h[f*h_stride + k] = h_c.
+ *
+ *  - With ow2 the combined stream is whitened: rx_c = g x + n with noise of unit variance
+ *    per complex sample whatever the branches' own variances, so wce_soft_demap's
+ *    |Hu|^2 (D0 - D1) on (rx_c, h_c) is a true LLR: the factor 1 / ow2[f] its comment says
+ *    to scale in by hand is already there.  With ow2 == NULL every weight is 1 and the
+ *    branches' common variance sigma^2 is preserved: rx_c = g x + n, var n = sigma^2.
+ *    A common factor on every ow2 changes no equalized symbol rx_c / h_c.
+ *  - A branch that is not live contributes nothing: the output is, bit for bit, that of
+ *    the call made on the live branches alone.  (This is how a lost branch arrives: the
+ *    _at calls give an undetected packet a NaN pre_fft, hence a NaN h row and a NaN
+ *    ow2.)  A packet with no live branch gets NaN in every entry the call writes for
+ *    it, entry 26 included.  A non-finite rx_a[b][k] of a live branch makes rx_c[b][k]
+ *    non-finite and changes nothing else.  No sum crosses subcarriers or packets: a
+ *    packet's bits depend only on its own data and the arguments.
+ *  - Asynchronous on `stream`; nothing is read back and nothing allocated; the ctx only
+ *    selects the device.  Each output may be NULL (not both); an absent output costs no
+ *    stores, and out->h alone reads no rx.  All offsets are 64-bit.
+ *  - WCE_EINVAL (text in wce_last_error()) before any launch: a NULL ctx, p, out, p->rx
+ *    or p->h; both outputs NULL; n_branches outside 1..8; n_frames < 0 or > 2^31 - 1; a
+ *    block stride < 53 or, with more than one frame, a frame stride < 14 block strides +
+ *    53 (p->rx and out->rx, each by its own strides); h_stride < 53 (p->h, out->h); with
+ *    more than one branch, a branch stride under which branches overlap: rx_branch_stride
+ *    must be >= 53 and either span a branch ((n_frames - 1) frame strides + 14 block strides
+ *    + 53), or fit the branches inside a block stride ((A - 1) branch strides + 53 <= block
+ *    stride), or between frame and block (>= 14 block strides + 53 and (A - 1) branch strides
+ *    + 14 block strides + 53 <= frame stride); h_branch_stride must be >= 53 and either
+ *    >= (n_frames - 1) h_stride + 53 or fit (A - 1) of it + 53 inside h_stride;
+ *    ow2_branch_stride >= n_frames; rx, h or an output not 16-byte aligned; ow2 not 8-byte
+ *    aligned.  n_frames == 0 is WCE_OK.
+ *
+ * wce_sync_share.  All antennas of a radio share one oscillator and see the packet at the
+ * same sample, but a branch in a fade misses its own detection and would arrive at the
+ * combiner dead although it has something to contribute at the right start.  For packet
+ * p < n_packets and branch a < n_branches let i(a) = a*branch_stride + p.  A branch is live
+ * when start[i] >= 0 (start != NULL) and metric[i] is finite; a* is the live branch with the
+ * largest metric, the lowest a on a tie.  If there is none nothing is written for p.
+ * Otherwise start[i(a)] = start[i(a*)] for every a (start != NULL) and cfo[i(a)] =
+ * cfo[i(a*)] (cfo != NULL).  In place, one thread per packet.  metric is
+ * wce_front_end_sync's, or wce_front_end_sync_stf's metric_ltf.  start == NULL shares the
+ * offset alone (live: a finite metric): for the path without a short field, where
+ * wce_front_end_preamble_at estimates each branch's offset once the shared start is known.
+ * A shared start that does not fit another branch's window falls to the _at calls' own
+ * guard.  Asynchronous on `stream`, nothing read back.  WCE_EINVAL: a NULL ctx or metric;
+ * start and cfo both NULL; n_branches outside 1..8; n_packets < 0 or > 2^31 - 1; with
+ * more than one branch, branch_stride < n_packets; start not 4-byte, metric or cfo not
+ * 8-byte aligned.  n_packets == 0 is WCE_OK. */
+#define WCE_COMBINE_MAX_BRANCHES 8
+
+typedef struct {
+    const wce_complex *rx;    /* device; rx[a*rx_branch_stride + f*rx_frame_stride + b*rx_block_stride + k] */
+    int64_t rx_branch_stride, rx_frame_stride, rx_block_stride;
+    const wce_complex *h;     /* device; h[a*h_branch_stride + f*h_stride + k] */
+    int64_t h_branch_stride, h_stride;
+    const double *ow2;        /* device; ow2[a*ow2_branch_stride + f]; NULL = unit weights */
+    int64_t ow2_branch_stride;
+    int32_t n_branches;       /* A, 1..WCE_COMBINE_MAX_BRANCHES */
+} wce_combine_par;
+
+typedef struct {              /* each pointer may be NULL = not wanted; not both */
+    wce_complex *rx;          /* rx[f*rx_frame_stride + b*rx_block_stride + k] = rx_c */
+    int64_t rx_frame_stride, rx_block_stride;
+    wce_complex *h;           /* h[f*h_stride + k] = h_c */
+    int64_t h_stride;
+} wce_combine_out;
+
+int wce_combine(wce_ctx *ctx, const wce_combine_par *p, int64_t n_frames, const wce_combine_out *out, void *stream);
+int wce_sync_share(wce_ctx *ctx, int32_t n_branches, int64_t branch_stride, int64_t n_packets, const double *metric,
+                   int32_t *start, double *cfo, void *stream);
+
 /* Non-finite guard.  The reference passes NaN/Inf through
  * silently: main.c's PS_MMSE returns NaN x 53 (main.c:148-212), a zero pilot
  * makes PS_* divide by zero (main.c:82-84), and its dimension checks only
