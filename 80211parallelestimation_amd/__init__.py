@@ -14,6 +14,7 @@ from .wce import (  # noqa: F401
     ChannelPar, FadingPar, pdp_taps, fading_taps,
     TRACK_KNOWN_TX, TRACK_PHASE, TRACK_REF_TX, Track, TrackOut,
     COMBINE_MAX_BRANCHES, CombinePar, CombineOut,
+    PsduPar, PsduOut, psdu_max_len,
 )
 
 __version__ = "0.1.0"

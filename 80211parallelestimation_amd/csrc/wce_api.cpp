@@ -1461,6 +1461,77 @@ int wce_reencode(wce_ctx *c, const wce_reencode_par *p, const wce_frames *in, in
     return rc ? fail(rc, "reencode launch") : WCE_OK;
 }
 
+// ---------------------------------------------------------------- framing the payload
+int wce_psdu_max_len(int32_t modulation, int32_t rate)
+{
+    const int T = wce::decode_info_bits(modulation, rate);
+    return T < 0 ? fail(WCE_EINVAL, "wce_psdu_max_len: unknown modulation or rate") : (T - 22) / 8;
+}
+
+// what both calls ask of p, n_frames and bits_stride; null when it holds, else what is wrong.  Fills T, nbytes,
+// max_len, length, seed, lengths, seeds, bits_stride and n of `a`
+static const char *check_psdu(const wce_psdu_par *p, int64_t n, int64_t bits_stride, bool framing, wce::PsduArgs *a)
+{
+    const int T = wce::decode_info_bits(p->modulation, p->rate);
+    if (T < 0) return "unknown modulation or rate";
+    const int32_t max = (T - 22) / 8;
+    if (!p->lengths && (p->length < 4 || p->length > max)) return "length outside 4..max";
+    if (framing && !p->seeds && (p->seed < 1 || p->seed > 127)) return "seed outside 1..127";
+    if (bits_stride < (T + 7) / 8) return "bits_stride < ceil(T / 8)";
+    if (reinterpret_cast<uintptr_t>(p->lengths) % 4) return "lengths not 4-byte aligned";
+    if (n < 0 || n > 0x7fffffffll) return "n_frames < 0 or > 2^31 - 1";
+    a->T = T; a->nbytes = (T + 7) / 8; a->max_len = max;
+    a->length = p->lengths ? max : p->length;
+    a->seed = framing && !p->seeds ? p->seed : 1;
+    a->lengths = p->lengths;
+    a->seeds = framing ? p->seeds : nullptr;
+    a->bits_stride = bits_stride; a->n = n;
+    return nullptr;
+}
+
+int wce_psdu_frame(wce_ctx *c, const wce_psdu_par *p, const uint8_t *payload, int64_t payload_stride, int64_t n,
+                   uint8_t *bits, int64_t bits_stride, void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    if (!p || !bits) return fail(WCE_EINVAL, "wce_psdu_frame: null parameters or bits");
+    wce::PsduArgs a{};
+    if (const char *what = check_psdu(p, n, bits_stride, true, &a))
+        return fail(WCE_EINVAL, (std::string("wce_psdu_frame: ") + what).c_str());
+    if (!payload && (p->lengths || p->length > 4))
+        return fail(WCE_EINVAL, "wce_psdu_frame: payload NULL with length > 4 or with lengths");
+    if (payload && payload_stride < a.length - 4)
+        return fail(WCE_EINVAL, "wce_psdu_frame: payload_stride < L - 4 (max - 4 with lengths)");
+    if (n == 0) return WCE_OK;
+    a.payload = payload; a.payload_stride = payload ? payload_stride : 0;
+    a.bits_w = bits;
+    DeviceGuard g(c->device);
+    const int rc = wce::launch_psdu_frame(a, stream);
+    return rc ? fail(rc, "psdu frame launch") : WCE_OK;
+}
+
+int wce_psdu_deframe(wce_ctx *c, const wce_psdu_par *p, const uint8_t *bits, int64_t bits_stride, int64_t n,
+                     const wce_psdu_out *out, void *stream)
+{
+    if (!c) return fail(WCE_EINVAL, "null ctx");
+    if (!p || !bits || !out) return fail(WCE_EINVAL, "wce_psdu_deframe: null parameters, bits or outputs");
+    if (!out->psdu && !out->seed && !out->fcs_ok && !out->n_good)
+        return fail(WCE_EINVAL, "wce_psdu_deframe: no output requested");
+    wce::PsduArgs a{};
+    if (const char *what = check_psdu(p, n, bits_stride, false, &a))
+        return fail(WCE_EINVAL, (std::string("wce_psdu_deframe: ") + what).c_str());
+    if (out->psdu && out->psdu_stride < a.length)
+        return fail(WCE_EINVAL, "wce_psdu_deframe: psdu_stride < L (max with lengths)");
+    if (reinterpret_cast<uintptr_t>(out->fcs_ok) % 4 || reinterpret_cast<uintptr_t>(out->n_good) % 4)
+        return fail(WCE_EINVAL, "wce_psdu_deframe: fcs_ok or n_good not 4-byte aligned");
+    if (n == 0) return WCE_OK;
+    a.bits_r = bits;
+    a.psdu = out->psdu; a.psdu_stride = out->psdu_stride;
+    a.oseed = out->seed; a.fcs_ok = out->fcs_ok; a.n_good = out->n_good;
+    DeviceGuard g(c->device);
+    const int rc = wce::launch_psdu_deframe(a, stream);
+    return rc ? fail(rc, "psdu deframe launch") : WCE_OK;
+}
+
 // ---------------------------------------------------------------- transmitter and channel
 static bool misaligned(const void *p, uintptr_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
 

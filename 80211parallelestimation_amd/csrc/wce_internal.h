@@ -372,6 +372,26 @@ struct SyncShareArgs {
     int32_t na;
 };
 
+// DATA-field framing and deframing (wce_psdu.hip): rows of ceil(T / 8) bytes at bits[f*bits_stride]; frame f's
+// PSDU length is lengths[f] (null: length), its scrambler seed seeds[f] (null: seed; framing only)
+struct PsduArgs {
+    int32_t T, nbytes, max_len;   // information bits, ceil(T / 8), (T - 22) / 8
+    int32_t length, seed;
+    const int32_t *lengths;
+    const uint8_t *seeds;
+    int64_t bits_stride, n;
+    const uint8_t *payload;       // framing: payload[f*payload_stride + i], i < L - 4
+    int64_t payload_stride;
+    uint8_t *bits_w;              // framing: the rows written
+    const uint8_t *bits_r;        // deframing: the rows read
+    uint8_t *psdu;                // deframing: each output may be null, not all
+    int64_t psdu_stride;
+    uint8_t *oseed;
+    uint32_t *fcs_ok, *n_good;
+};
+
+int launch_psdu_frame(const PsduArgs &a, void *stream);
+int launch_psdu_deframe(const PsduArgs &a, void *stream);
 int launch_combine(const CombineArgs &a, void *stream);
 int launch_sync_share(const SyncShareArgs &a, void *stream);
 int launch_modulate(const TxArgs &a, void *stream);
@@ -517,7 +537,8 @@ constexpr int WCE_VARIANT_GRID = 6;    // the receive and transmit chain's loopi
                                       // launch_sync_stf, launch_short_field,
                                       // launch_demod's builds without evm / nerr, launch_demap, launch_viterbi,
                                       // launch_reencode, the three transmit launches, launch_combine,
-                                      // launch_sync_share): 0 = each its own grid cap
+                                      // launch_sync_share, launch_psdu_frame, launch_psdu_deframe): 0 = each its
+                                      // own grid cap
                                       // (default), else at most CHAIN_TEST_GRID workgroups, so that a few dozen frames
                                       // make every wave loop over several, the last trip ragged.  A test seam, not an
                                       // A/B: a frame's outputs depend on its own data alone, so the bits are those of 0.

@@ -144,6 +144,18 @@ class ReencodeOut(ctypes.Structure):
                 ("h_stride", c_int64)]
 
 
+class PsduPar(ctypes.Structure):
+    """struct wce_psdu_par (include/wce.h)."""
+    _fields_ = [("modulation", c_int32), ("rate", c_int32), ("length", c_int32), ("seed", c_int32),
+                ("lengths", c_void_p), ("seeds", c_void_p)]
+
+
+class PsduOut(ctypes.Structure):
+    """struct wce_psdu_out (include/wce.h)."""
+    _fields_ = [("psdu", c_void_p), ("psdu_stride", c_int64), ("seed", c_void_p), ("fcs_ok", c_void_p),
+                ("n_good", c_void_p)]
+
+
 class ChannelPar(ctypes.Structure):
     """struct wce_channel_par (include/wce.h)."""
     _fields_ = [("taps", c_void_p), ("taps_stride", c_int64), ("n_taps", c_int32), ("field", c_int32),
@@ -234,6 +246,9 @@ ABI = {
                            c_int64, c_void_p, c_int64, c_void_p, c_void_p],
     "wce_decode_info_bits": [c_int32, c_int32],
     "wce_reencode": [c_void_p, POINTER(ReencodePar), POINTER(Frames), c_int64, POINTER(ReencodeOut), c_void_p],
+    "wce_psdu_max_len": [c_int32, c_int32],
+    "wce_psdu_frame": [c_void_p, POINTER(PsduPar), c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p],
+    "wce_psdu_deframe": [c_void_p, POINTER(PsduPar), c_void_p, c_int64, c_int64, POINTER(PsduOut), c_void_p],
     "wce_modulate": [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int64, c_void_p, c_int64,
                      c_void_p],
     "wce_channel": [c_void_p, c_void_p, c_int64, c_int64, c_int64, POINTER(ChannelPar), c_void_p, c_int64, c_int64,
@@ -325,6 +340,15 @@ def info_bits(modulation, rate) -> int:
     if T < 0:
         raise WceError(T, "wce_decode_info_bits")
     return T
+
+
+def psdu_max_len(modulation, rate) -> int:
+    """wce_psdu_max_len: the longest PSDU, FCS included, a frame of `modulation` at `rate` carries:
+    (info_bits - 22) // 8 octets."""
+    n = load().wce_psdu_max_len(int(modulation), int(rate))
+    if n < 0:
+        raise WceError(n, "wce_psdu_max_len")
+    return n
 
 
 def device_count() -> int:
@@ -737,6 +761,83 @@ class Context:
         _check(_lib.wce_reencode(self.handle, byref(p), byref(frames) if frames is not None else None, n_frames,
                                  byref(o), stream), "wce_reencode")
 
+    def psdu_frame(self, payload, n_frames, modulation, rate, length=None, lengths=None, seed=93, seeds=None,
+                   bits=None, payload_stride=None, bits_stride=None, stream=None):
+        """wce_psdu_frame on device arrays: payload uint8 [n][payload_stride], the PSDU octets in front of the FCS
+        (length - 4 of them; None where every frame has length 4) -> bits uint8 [n][bits_stride], the frame's
+        info_bits(modulation, rate) information bits packed as reencode reads them: 16 SERVICE bits, the payload
+        and its CRC-32 FCS, six tail bits and the pad, scrambled from `seed` (1..127) with the tail zeroed.
+        length is the PSDU length with the FCS, 4..psdu_max_len (None: the longest); lengths int32 [n] and seeds
+        uint8 [n] give every frame its own (a frame whose entry is out of range gets a row of zeros).  The strides
+        default to max - 4 (length - 4 without lengths) and ceil(T / 8)."""
+        nbytes, mx = (info_bits(modulation, rate) + 7) // 8, psdu_max_len(modulation, rate)
+        L = mx if length is None else int(length)
+        p = PsduPar(modulation, rate, L, int(seed), _addr(lengths), _addr(seeds))
+        ps = payload_stride if payload_stride is not None else (mx if lengths is not None else L) - 4
+        _check(_lib.wce_psdu_frame(self.handle, byref(p), _addr(payload), ps, n_frames, _addr(bits),
+                                   bits_stride if bits_stride is not None else nbytes, stream), "wce_psdu_frame")
+
+    def psdu_deframe(self, bits, n_frames, modulation, rate, length=None, lengths=None, psdu=None, seed=None,
+                     fcs_ok=None, n_good=None, bits_stride=None, psdu_stride=None, stream=None):
+        """wce_psdu_deframe on device arrays: bits uint8 [n][bits_stride] (viterbi_decode's packed rows, decoded
+        with terminated=False) -> psdu uint8 [n][psdu_stride], the descrambled PSDU octets with their FCS
+        (length of them, or lengths[n]; nothing beyond is written), seed uint8 [n], the scrambler state the
+        first seven bits give (0: they are all zero, and the PSDU is written undescrambled), fcs_ok uint32 [n]
+        (1: the CRC-32 over the PSDU leaves the residue) and n_good uint32 [1], to which the number of good
+        frames is ADDED.  Each output is optional.  A frame whose lengths entry is out of range: fcs_ok 0, seed 0,
+        no PSDU octet written.  The strides default to ceil(T / 8) and max (length without lengths)."""
+        nbytes, mx = (info_bits(modulation, rate) + 7) // 8, psdu_max_len(modulation, rate)
+        L = mx if length is None else int(length)
+        p = PsduPar(modulation, rate, L, 0, _addr(lengths), None)
+        o = PsduOut(_addr(psdu), psdu_stride if psdu_stride is not None else (mx if lengths is not None else L),
+                    _addr(seed), _addr(fcs_ok), _addr(n_good))
+        _check(_lib.wce_psdu_deframe(self.handle, byref(p), _addr(bits),
+                                     bits_stride if bits_stride is not None else nbytes, n_frames, byref(o), stream),
+               "wce_psdu_deframe")
+
+    def psdu_frame_host(self, payloads, modulation, rate, seeds=93):
+        """Convenience: host payloads, a list of byte rows (bytes or uint8 arrays, each 0..psdu_max_len - 4 long,
+        their lengths free) or a 2-D uint8 array, and seeds (a scalar or [B]) -> bits uint8 [B][T], one framed
+        information bit per entry (psdu_frame, unpacked)."""
+        rows = [np.frombuffer(bytes(r), np.uint8) if isinstance(r, (bytes, bytearray)) else np.asarray(r, np.uint8)
+                for r in payloads]
+        B, T, mx = len(rows), info_bits(modulation, rate), psdu_max_len(modulation, rate)
+        if any(r.ndim != 1 or r.size > mx - 4 for r in rows):
+            raise ValueError(f"each payload must be a byte row of at most {mx - 4} octets")
+        pay = np.zeros((B, mx - 4), np.uint8)
+        for f, r in enumerate(rows):
+            pay[f, :r.size] = r
+        lengths = np.array([r.size + 4 for r in rows], np.int32)
+        sd = np.broadcast_to(np.asarray(seeds, np.int64), (B,))
+        if np.any(sd < 1) or np.any(sd > 127):
+            raise ValueError("seeds must be 1..127")
+        sd = np.ascontiguousarray(sd.astype(np.uint8))
+        dbits = DeviceArray((B, (T + 7) // 8), np.uint8, zero=True)
+        keep = (DeviceArray.from_numpy(pay), DeviceArray.from_numpy(lengths), DeviceArray.from_numpy(sd))
+        self.psdu_frame(keep[0], B, modulation, rate, lengths=keep[1], seeds=keep[2], bits=dbits)
+        synchronize()
+        return np.unpackbits(dbits.numpy(), axis=1, bitorder="little")[:, :T]
+
+    def psdu_deframe_host(self, bits, modulation, rate, lengths):
+        """Convenience: host bits [B][T] (one information bit per entry, as decode_host returns them) and the PSDU
+        lengths (a scalar or [B], FCS included) -> dict of host arrays: psdu uint8 [B][max] (row f holds
+        lengths[f] octets, the rest 0), seed uint8 [B], fcs_ok uint32 [B] and n_good, their number (psdu_deframe)."""
+        bits = np.asarray(bits, np.uint8)
+        T, mx = info_bits(modulation, rate), psdu_max_len(modulation, rate)
+        if bits.ndim != 2 or bits.shape[1] != T:
+            raise ValueError("bits must be [B][T] with T = info_bits(modulation, rate)")
+        B = bits.shape[0]
+        ln = np.ascontiguousarray(np.broadcast_to(np.asarray(lengths), (B,)).astype(np.int32))
+        dbits = DeviceArray.from_numpy(np.packbits(bits, axis=1, bitorder="little"))
+        dlen = DeviceArray.from_numpy(ln)
+        d = {"psdu": DeviceArray((B, mx), np.uint8, zero=True), "seed": DeviceArray((B,), np.uint8, zero=True),
+             "fcs_ok": DeviceArray((B,), np.uint32, zero=True), "n_good": DeviceArray((1,), np.uint32, zero=True)}
+        self.psdu_deframe(dbits, B, modulation, rate, lengths=dlen, **d)
+        synchronize()
+        res = {n: a.numpy() for n, a in d.items()}
+        res["n_good"] = int(res["n_good"][0])
+        return res
+
     def modulate(self, sym, n_frames, wave, n_blocks=NBLK, tx_pre=None, pre_stride=0, frame_stride=None,
                  block_stride=NSC, wave_stride=None, stream=None):
         """wce_modulate on device arrays: sym complex [n][n_blocks][block_stride] (53 bins a block, e.g. reencode's
@@ -933,7 +1034,7 @@ class Context:
 
     def link_host(self, modulation, rate, snr_db, n_frames, sources=(LT_LS, PS_LINEAR, PS_MMSE), taps=None, cfo=None,
                   delay=None, capture_len=1488, threshold=0.25, backoff=0, seed=0x80211, dd_iterations=0,
-                  scale=8.8753, stf=False, stf_threshold=0.25, knot_period=80, tracker=None):
+                  scale=8.8753, stf=False, stf_threshold=0.25, psdu_len=None, knot_period=80, tracker=None):
         """The experiment WiFi_RX.m:4-9 announces (SNR, channel_model, FO), for a batch, scored in coded bit
         errors: n_frames packets of random information bits (drawn on the host from `seed`, the last six 0) are
         re-encoded to symbols with 802.11's pilots, transmitted behind the context's tx preamble through `taps`
@@ -961,8 +1062,18 @@ class Context:
         1520 + n_taps - 1 + the largest delay samples (1,648 is a window with room for 128 more), else ValueError.
         -> {source: nbiterr uint32 [B]} plus "start" int32 [B] (-1: not detected; its counts are those of an
         all-zero decode), "metric" [B], "cfo" [B] (the estimate), "ow2" [B] and "bits" uint8 [B][T]; with
-        tracker, "tracked": {source: nbiterr uint32 [B]} of the tracked runs."""
+        tracker, "tracked": {source: nbiterr uint32 [B]} of the tracked runs.
+        psdu_len L (4..psdu_max_len): the packets carry real PSDUs and are judged as a receiver in the field
+        judges them.  Payload octets rng.integers(0, 256, (B, L - 4)) and scrambler seeds rng.integers(1, 128, B)
+        are drawn from `seed` instead of the bits, framed on the device (psdu_frame) and fed to reencode; every
+        decode runs unterminated (the tail is not at the end of the field) against the framed bits, and
+        psdu_deframe is queued behind each source's last decoder and each tracked one.  The result gains
+        "fcs_ok" {source: uint32 [B]}, "psdu_rx" {source: uint8 [B][L]}, "seed_rx" {source: uint8 [B]}, "bits_rx"
+        {source: uint8 [B][T]} (the decoded rows), "payload" uint8 [B][L - 4], "seeds" uint8 [B] and, with tracker,
+        "tracked_fcs_ok" {source: uint32 [B]}; "bits" is the framed bits."""
         B, T = int(n_frames), info_bits(modulation, rate)
+        if psdu_len is not None and not 4 <= int(psdu_len) <= psdu_max_len(modulation, rate):
+            raise ValueError(f"psdu_len must be 4..{psdu_max_len(modulation, rate)} octets")
         if tracker is not None and dd_iterations:
             raise ValueError("tracker with dd_iterations > 0 (decoder-in-the-loop tracking) is not built")
         if tracker is not None:
@@ -979,11 +1090,16 @@ class Context:
             if capture_len < need:
                 raise ValueError(f"capture_len {capture_len} cannot hold a packet with a short field: {need} samples")
         rng = np.random.default_rng(seed)
-        bits = rng.integers(0, 2, (B, T), dtype=np.uint8)
-        bits[:, T - 6:] = 0
+        if psdu_len is None:
+            bits = rng.integers(0, 2, (B, T), dtype=np.uint8)
+            bits[:, T - 6:] = 0
+            dbits = DeviceArray.from_numpy(np.packbits(bits, axis=1, bitorder="little"))
+            ref, term = bits, True
+        else:
+            dbits, framed = self._psdu_draw(rng, B, 1, modulation, rate, int(psdu_len))
+            ref, term = dbits, False
         ow2 = np.ascontiguousarray(np.broadcast_to(
             (52.0 * scale * scale / 4096.0) / 10.0 ** (np.asarray(snr_db, np.float64) / 10.0), (B,)))
-        dbits = DeviceArray.from_numpy(np.packbits(bits, axis=1, bitorder="little"))
         dtx = DeviceArray((B, NBLK, NSC), zero=True)
         dpre = DeviceArray.from_numpy(self.tx_pre)
         dfield = DeviceArray((160,), zero=True)   # the clean field: its samples 32..95 are one period, sync's ltf
@@ -1019,24 +1135,60 @@ class Context:
             h = outs[names[s]]
             hlt = None if s == LT_LS else outs["lt_ls"]
             dem = self._demod_device(fr, B, h, hlt, modulation, scale, True, True)
-            dec = self._decode_device(dem["eq"], h, hlt, B, modulation, rate, scale, True, bits)
-            dd = self._dd_device(fr, B, dec["bits"], dem["theta"], modulation, rate, scale, True, dec["_ref"],
+            dec = self._decode_device(dem["eq"], h, hlt, B, modulation, rate, scale, term, ref)
+            dd = self._dd_device(fr, B, dec["bits"], dem["theta"], modulation, rate, scale, term, dec["_ref"],
                                  int(dd_iterations)) if dd_iterations else None
             runs[s] = (dem, dec, dd)
         tracked = {}
         if tracker is not None:
             for s in sources:
                 trk = self._track_device(fr, B, outs[names[s]], mu, beta, modulation, scale, True, True)
-                tracked[s] = (trk, self._decode_device(trk["eq"], None, None, B, modulation, rate, scale, True, bits,
+                tracked[s] = (trk, self._decode_device(trk["eq"], None, None, B, modulation, rate, scale, term, ref,
                                                        h_blocks=trk["h_blocks"]))
+        if psdu_len is not None:
+            rx = {s: self._psdu_device((dd if dd is not None else dec)["bits"], B, modulation, rate, int(psdu_len))
+                  for s, (dem, dec, dd) in runs.items()}
+            trx = {s: self._psdu_device(dec["bits"], B, modulation, rate, int(psdu_len))
+                   for s, (trk, dec) in tracked.items()}
         synchronize()
         res = {s: (dd if dd is not None else dec)["nbiterr"].numpy() for s, (dem, dec, dd) in runs.items()}
         if tracker is not None:
             res["tracked"] = {s: dec["nbiterr"].numpy() for s, (trk, dec) in tracked.items()}
-        res.update(start=dstart.numpy(), metric=dmetric.numpy(), cfo=dcfo.numpy(), ow2=ow2, bits=bits)
+        res.update(start=dstart.numpy(), metric=dmetric.numpy(), cfo=dcfo.numpy(), ow2=ow2)
+        if psdu_len is None:
+            res["bits"] = bits
+        else:
+            res.update(bits=np.unpackbits(dbits.numpy(), axis=1, bitorder="little")[:, :T], payload=framed[0],
+                       seeds=framed[1], fcs_ok={s: d["fcs_ok"].numpy() for s, d in rx.items()},
+                       psdu_rx={s: d["psdu"].numpy() for s, d in rx.items()},
+                       seed_rx={s: d["seed"].numpy() for s, d in rx.items()},
+                       bits_rx={s: np.unpackbits((dd if dd is not None else dec)["bits"].numpy(), axis=1,
+                                                 bitorder="little")[:, :T] for s, (dem, dec, dd) in runs.items()})
+            if tracker is not None:
+                res["tracked_fcs_ok"] = {s: d["fcs_ok"].numpy() for s, d in trx.items()}
         if stf:
             res["metric_stf"] = dmstf.numpy()
         return res
+
+    def _psdu_draw(self, rng, B, copies, modulation, rate, L):
+        """link_host's packets with PSDUs: payload octets [B][L - 4] and scrambler seeds [B] from rng, framed on
+        the device `copies` times over (frame a B + f is packet f) -> (packed bits DeviceArray [copies B][ceil(T / 8)],
+        (payload, seeds))"""
+        payload = rng.integers(0, 256, (B, L - 4)).astype(np.uint8)
+        seeds = rng.integers(1, 128, B).astype(np.uint8)
+        dbits = DeviceArray((copies * B, (info_bits(modulation, rate) + 7) // 8), np.uint8, zero=True)
+        dpay = DeviceArray.from_numpy(np.tile(payload, (copies, 1))) if L > 4 else None
+        dseeds = DeviceArray.from_numpy(np.tile(seeds, copies))
+        self.psdu_frame(dpay, copies * B, modulation, rate, length=L, seeds=dseeds, bits=dbits)
+        synchronize()   # the payload and the seeds are free to go
+        return dbits, (payload, seeds)
+
+    def _psdu_device(self, dbits, n, modulation, rate, L):
+        """queue psdu_deframe behind a decoder's packed bits -> name -> DeviceArray (read after a synchronize)"""
+        d = {"psdu": DeviceArray((n, L), np.uint8, zero=True), "seed": DeviceArray((n,), np.uint8, zero=True),
+             "fcs_ok": DeviceArray((n,), np.uint32, zero=True)}
+        self.psdu_deframe(dbits, n, modulation, rate, length=L, **d)
+        return d
 
     def combine(self, rx, h, n_frames, n_branches, ow2=None, out_rx=None, out_h=None, rx_branch_stride=None,
                 rx_frame_stride=None, rx_block_stride=NSC, h_branch_stride=None, h_stride=NSC,
@@ -1091,7 +1243,7 @@ class Context:
     def link_mrc_host(self, modulation, rate, snr_db, n_frames, n_rx, taps, sources=(LT_LS, PS_LINEAR, PS_MMSE),
                       branch_loss_db=None, share_sync=True, weighted=True, cfo=None, delay=None, capture_len=1488,
                       threshold=0.25, backoff=0, seed=0x80211, dd_iterations=0, scale=8.8753, stf=False,
-                      stf_threshold=0.25, knot_period=80, tracker=None, keep_capture=False):
+                      stf_threshold=0.25, knot_period=80, tracker=None, keep_capture=False, psdu_len=None):
         """link_host behind n_rx receive antennas: n_frames packets of random information bits (link_host's draw
         from `seed`) are re-encoded once and transmitted once per branch on the same symbols, through that
         branch's taps ([A][n_taps], or [A][B][n_taps]; with a knot axis, [A][B][K][n_taps], through transmit_tv)
@@ -1107,8 +1259,14 @@ class Context:
         the same per source for the tracked runs; plus "start" int32, "metric", "cfo", "ow2" (the transmitter's)
         and "ow2_est" (the front end's), each [A][B], after sharing, and "bits" uint8 [B][T]; with stf,
         "metric_stf"; with keep_capture, "capture" complex [A][B][capture_len].  n_rx = 1 gives link_host's
-        counts as branch 0."""
+        counts as branch 0.
+        psdu_len L: as link_host -- the same draws, every branch sends the same framed bits, the decodes run
+        unterminated and psdu_deframe follows each chain's last decoder.  The result gains "fcs_ok" {source:
+        {"combined": uint32 [B], "branch": uint32 [A][B]}}, "psdu_rx" {source: uint8 [B][L]} (the combined
+        chain's), "payload", "seeds" and, with tracker, "tracked_fcs_ok" like "fcs_ok"."""
         A, B, T = int(n_rx), int(n_frames), info_bits(modulation, rate)
+        if psdu_len is not None and not 4 <= int(psdu_len) <= psdu_max_len(modulation, rate):
+            raise ValueError(f"psdu_len must be 4..{psdu_max_len(modulation, rate)} octets")
         if not 1 <= A <= COMBINE_MAX_BRANCHES:
             raise ValueError("n_rx must be 1..8")
         if tracker is not None and dd_iterations:
@@ -1133,13 +1291,19 @@ class Context:
                 raise ValueError(f"capture_len {capture_len} cannot hold a packet with a short field: {need} samples")
         N, L = A * B, int(capture_len)
         rng = np.random.default_rng(seed)
-        bits = rng.integers(0, 2, (B, T), dtype=np.uint8)
-        bits[:, T - 6:] = 0
+        if psdu_len is None:
+            bits = rng.integers(0, 2, (B, T), dtype=np.uint8)
+            bits[:, T - 6:] = 0
+            all_bits = np.tile(bits, (A, 1))
+            dbits = DeviceArray.from_numpy(np.packbits(all_bits, axis=1, bitorder="little"))
+            term = True
+        else:   # the references stay on the device: the first B rows of dbits are the packets themselves
+            dbits, framed = self._psdu_draw(rng, B, A, modulation, rate, int(psdu_len))
+            all_bits = bits = dbits
+            term = False
         ow2 = np.ascontiguousarray(np.broadcast_to(
             (52.0 * scale * scale / 4096.0) / 10.0 ** (np.asarray(snr_db, np.float64) / 10.0), (B,))[None] *
             10.0 ** (loss / 10.0)[:, None])
-        all_bits = np.tile(bits, (A, 1))
-        dbits = DeviceArray.from_numpy(np.packbits(all_bits, axis=1, bitorder="little"))
         dtx = DeviceArray((N, NBLK, NSC), zero=True)   # the same symbols once per branch: frame a B + f is packet f
         dpre = DeviceArray.from_numpy(self.tx_pre)
         dfield = DeviceArray((160,), zero=True)
@@ -1188,15 +1352,20 @@ class Context:
 
         def chains(frames, n, h, hlt, ref):   # link_host's runs on n frames -> (static or dd decode, tracked decode)
             dem = self._demod_device(frames, n, h, hlt, modulation, scale, True, True)
-            dec = self._decode_device(dem["eq"], h, hlt, n, modulation, rate, scale, True, ref)
-            dd = self._dd_device(frames, n, dec["bits"], dem["theta"], modulation, rate, scale, True, dec["_ref"],
+            dec = self._decode_device(dem["eq"], h, hlt, n, modulation, rate, scale, term, ref)
+            dd = self._dd_device(frames, n, dec["bits"], dem["theta"], modulation, rate, scale, term, dec["_ref"],
                                  int(dd_iterations)) if dd_iterations else None
             trk = tdec = None
             if tracker is not None:
                 trk = self._track_device(frames, n, h, mu, beta, modulation, scale, True, True)
-                tdec = self._decode_device(trk["eq"], None, None, n, modulation, rate, scale, True, ref,
+                tdec = self._decode_device(trk["eq"], None, None, n, modulation, rate, scale, term, ref,
                                            h_blocks=trk["h_blocks"])
-            return (dd if dd is not None else dec), tdec, (dem, dec, dd, trk)
+            last = dd if dd is not None else dec
+            if psdu_len is not None:
+                last = dict(last, _psdu=self._psdu_device(last["bits"], n, modulation, rate, int(psdu_len)))
+                if tdec is not None:
+                    tdec["_psdu"] = self._psdu_device(tdec["bits"], n, modulation, rate, int(psdu_len))
+            return last, tdec, (dem, dec, dd, trk)
         runs = {}
         for s in sources:
             h = outs[names[s]]
@@ -1211,6 +1380,15 @@ class Context:
             res["tracked"] = {s: {"combined": comb[1]["nbiterr"].numpy(),
                                   "branch": alone[1]["nbiterr"].numpy().reshape(A, B)}
                               for s, (alone, comb, _, _) in runs.items()}
+        if psdu_len is not None:
+            flags = lambda i: {s: {"combined": comb[i]["_psdu"]["fcs_ok"].numpy(),
+                                   "branch": alone[i]["_psdu"]["fcs_ok"].numpy().reshape(A, B)}
+                               for s, (alone, comb, _, _) in runs.items()}
+            res.update(fcs_ok=flags(0), payload=framed[0], seeds=framed[1],
+                       psdu_rx={s: comb[0]["_psdu"]["psdu"].numpy() for s, (alone, comb, _, _) in runs.items()})
+            if tracker is not None:
+                res["tracked_fcs_ok"] = flags(1)
+            bits = np.unpackbits(dbits.rows(0, B), axis=1, bitorder="little")[:, :T]
         res.update(start=dstart.numpy().reshape(A, B), metric=dmetric.numpy().reshape(A, B),
                    cfo=dcfo.numpy().reshape(A, B), ow2=ow2, ow2_est=dow2e.numpy().reshape(A, B), bits=bits)
         if stf:
@@ -1258,7 +1436,10 @@ class Context:
         d = {"llr": DeviceArray((B, NBLK, 48 * modulation), np.float32, zero=True),
              "bits": DeviceArray((B, (T + 7) // 8), np.uint8, zero=True)}
         dref = None
-        if ref_bits is not None:
+        if isinstance(ref_bits, DeviceArray):   # packed rows [>= B][ceil(T / 8)] already there
+            dref = ref_bits
+            d["nbiterr"] = DeviceArray((B,), np.uint32, zero=True)
+        elif ref_bits is not None:
             ref = np.asarray(ref_bits, np.uint8)
             if ref.shape != (B, T):
                 raise ValueError("ref_bits must be [B][T] with T = info_bits(modulation, rate)")

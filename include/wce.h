@@ -772,6 +772,76 @@ typedef struct {              /* each pointer may be NULL = not wanted; not both
 int wce_reencode(wce_ctx *ctx, const wce_reencode_par *p, const wce_frames *in, int64_t n_frames,
                  const wce_reencode_out *out, void *stream);
 
+/* ---- framing the payload: SERVICE, PSDU, tail and pad, scrambler, CRC-32 FCS (IEEE
+ * 802.11-2020 17.3.5.2 to 17.3.5.5 and 9.2.4.8; the reference stops at channel estimates) ----
+ * A receiver in the field has no reference bits: it descrambles the DATA field, cuts the
+ * PSDU out of it and checks the frame check sequence.  wce_psdu_frame builds the T =
+ * wce_decode_info_bits(modulation, rate) information bits of a frame from a payload, packed
+ * as wce_reencode reads them; wce_psdu_deframe takes the rows wce_viterbi_decode writes
+ * (decode with flags = 0: the tail is not at the end of the field, so the encoder does not
+ * end in state 0) back to the PSDU and says whether its FCS holds.
+ *
+ *   L          the PSDU length in octets, the 4 of the FCS included: 4 <= L <= max =
+ *              wce_psdu_max_len(modulation, rate) = (T - 22) / 8 rounded down (42 at BPSK 1/2,
+ *              402 at 64-QAM 3/4).
+ *   field      bit t before scrambling: t = 0..15 SERVICE, 0;  t = 16 + 8 i + j bit j (LSB
+ *              first) of PSDU octet i < L;  the next six bits the tail;  the rest, up to T - 1,
+ *              pad, 0 (there always is some).  PSDU octet i is byte i + 2 of a packed row.
+ *   scrambler  x^7 + x^4 + 1: state x1..x7, each step outputs s = x4 ^ x7, then x7 <- x6 ..
+ *              x2 <- x1, x1 <- s; bit i - 1 of the seed (1..127) is the initial x_i, so
+ *              s_t = s_(t-4) ^ s_(t-7) from t = 7 on.  Seed 127 sends 00001110 11110010 ..., seed 93
+ *              (x7..x1 = 1011101) 01101100 00011001 ...  Information bit t = field bit t ^ s_t,
+ *              but the six tail positions, which are 0 after scrambling.
+ *   FCS        CRC-32 (polynomial 0x04C11DB7, register preset to ones, result complemented:
+ *              zlib's crc32, "123456789" -> 0xCBF43926) over PSDU octets 0 .. L - 5, stored in
+ *              octets L - 4 .. L - 1, least significant octet first.  A good PSDU has
+ *              crc32(all L octets) == 0x2144DF1C.
+ *
+ *  - wce_psdu_frame reads payload[f*payload_stride + i], i < L_f - 4 (nothing with L_f = 4;
+ *    payload may be NULL when every frame has L = 4), appends the FCS, scrambles with the
+ *    frame's seed and writes bits[f*bits_stride + (t >> 3)], bit t & 7; the unused high bits of
+ *    the last byte are 0 and bytes of a row beyond ceil(T / 8) are not touched.
+ *  - wce_psdu_deframe takes the first seven bits of a row as s_0..s_6 (SERVICE bits 0..6 are
+ *    0), continues the sequence by the recurrence and descrambles.  out->seed[f] is the
+ *    initial state that sends those seven bits.  If all seven are 0 (what an undetected
+ *    packet's all-zero decode gives) seed = 0, fcs_ok = 0 and the PSDU is written
+ *    undescrambled.  out->psdu[f*psdu_stride + i], i < L_f, and nothing beyond; fcs_ok[f] = 1
+ *    where the CRC over the L_f octets leaves the residue; *n_good += the number of such
+ *    frames (one atomic add per workgroup).  SERVICE bits 7..15, the tail and the pad are not
+ *    checked (the standard's receiver ignores them).  p->seed and p->seeds are ignored.
+ *  - p->lengths / p->seeds give every frame its own length / seed.  One that is out of range
+ *    cannot be refused on the host (nothing is read back): framing writes that frame's row
+ *    as zeros; deframing gives fcs_ok = 0, seed = 0 and writes no PSDU octet.  No other frame
+ *    changes: a frame's result depends only on its own row and the arguments.
+ *  - Asynchronous on `stream`; nothing is read back, nothing allocated, the ctx only selects
+ *    the device.  Rows need no alignment (45-byte strides are the normal case).  All offsets
+ *    are 64-bit.
+ *  - WCE_EINVAL (text in wce_last_error()) before any launch: a NULL ctx, p, bits or out;
+ *    every output NULL; payload NULL with length > 4 or with lengths; an unknown modulation
+ *    or rate; length outside 4..max (without lengths); seed outside 1..127 (framing, without
+ *    seeds); bits_stride < ceil(T / 8); payload_stride < max - 4 or psdu_stride < max with
+ *    lengths, else < L - 4 / < L; lengths, fcs_ok or n_good not 4-byte aligned; n_frames < 0
+ *    or > 2^31 - 1.  n_frames == 0 is WCE_OK. */
+typedef struct {
+    int32_t modulation, rate; /* WCE_MOD_*, WCE_RATE_*: they give T */
+    int32_t length;           /* L for every frame, where lengths == NULL */
+    int32_t seed;             /* 1..127 for every frame, where seeds == NULL (framing only) */
+    const int32_t *lengths;   /* device, [n_frames], each 4..max; NULL = length */
+    const uint8_t *seeds;     /* device, [n_frames], each 1..127; NULL = seed (framing only) */
+} wce_psdu_par;
+typedef struct {              /* each pointer may be NULL = not wanted; not all */
+    uint8_t *psdu;            /* psdu[f*psdu_stride + i], i < L_f: the descrambled octets, FCS included */
+    int64_t psdu_stride;
+    uint8_t *seed;            /* [n_frames]: the recovered seed, 0 = none */
+    uint32_t *fcs_ok;         /* [n_frames]: 1 good, 0 bad */
+    uint32_t *n_good;         /* one counter: the call ADDS the number of good frames */
+} wce_psdu_out;
+int wce_psdu_max_len(int32_t modulation, int32_t rate);
+int wce_psdu_frame(wce_ctx *ctx, const wce_psdu_par *p, const uint8_t *payload, int64_t payload_stride,
+                   int64_t n_frames, uint8_t *bits, int64_t bits_stride, void *stream);
+int wce_psdu_deframe(wce_ctx *ctx, const wce_psdu_par *p, const uint8_t *bits, int64_t bits_stride,
+                     int64_t n_frames, const wce_psdu_out *out, void *stream);
+
 /* ---- transmitter and channel: symbols -> clean waveform -> raw capture windows (the
  * reference's WiFi_RX.m:4-9 declares SNR, channel_model, FO and Pawgn and uses none of
  * them: its input is one recorded capture) ----
