@@ -516,6 +516,14 @@ static wce::Workspace *stream_ws(wce_ctx *c, void *stream, std::unique_lock<std:
     return w;
 }
 
+// the size a stream's scratch is created with for a batch of n frames: wce_ctx_reserve's size is the minimum.
+// Scratch that exists is never re-sized to it: growing waits for the stream, and a reserved stream must not wait.
+static int64_t hinted(wce_ctx *c, int64_t n)
+{
+    std::lock_guard<std::mutex> g(c->ws_mu);
+    return c->ws_hint > n ? c->ws_hint : n;
+}
+
 int wce_ctx_reserve_stream(wce_ctx *c, int64_t n, void *stream)
 {
     if (!c) return fail(WCE_EINVAL, "null ctx");
@@ -523,7 +531,8 @@ int wce_ctx_reserve_stream(wce_ctx *c, int64_t n, void *stream)
     std::unique_lock<std::mutex> lk;
     wce::Workspace *w = stream_ws(c, stream, lk);
     if (!w) return fail(WCE_ENOMEM, "workspace entry");
-    return grow_ws(c, *w, n, stream);
+    // scratch created here is created "later" too: at least wce_ctx_reserve's size, as wce_estimate would make it
+    return grow_ws(c, *w, w->p ? n : hinted(c, n), stream);
 }
 
 int wce_ctx_reserve(wce_ctx *c, int64_t n)
@@ -665,12 +674,7 @@ static int estimate_impl(wce_ctx *c, const wce_frames *in, const wce_outputs *ou
         if (!w) {
             w = stream_ws(c, stream, lk);
             if (!w) return fail(WCE_ENOMEM, "workspace entry");
-            int64_t want = n;
-            {
-                std::lock_guard<std::mutex> hg(c->ws_mu);
-                if (c->ws_hint > want) want = c->ws_hint;
-            }
-            rc = grow_ws(c, *w, want, stream);
+            rc = grow_ws(c, *w, w->p ? n : hinted(c, n), stream);
             if (rc) return rc;
         } else if (w->frames < n) {
             return fail(WCE_EINVAL, "plan workspace too small");
@@ -1781,6 +1785,16 @@ int wce_event_create(void **ev)
 }
 int wce_event_destroy(void *ev) { HIPCHECK(hipEventDestroy((hipEvent_t)ev), "hipEventDestroy"); return WCE_OK; }
 int wce_event_record(void *ev, void *s) { HIPCHECK(hipEventRecord((hipEvent_t)ev, (hipStream_t)s), "hipEventRecord"); return WCE_OK; }
+int wce_event_query(void *ev)
+{
+    hipError_t e = hipEventQuery((hipEvent_t)ev);
+    if (e == hipSuccess) return 1;
+    if (e == hipErrorNotReady) {
+        (void)hipGetLastError();   /* pending is an answer, not an error left for the next call to find */
+        return 0;
+    }
+    return hipfail(e, "hipEventQuery");
+}
 int wce_event_elapsed_ms(float *ms, void *a, void *b)
 {
     HIPCHECK(hipEventSynchronize((hipEvent_t)b), "hipEventSynchronize");

@@ -291,6 +291,7 @@ ABI = {
     "wce_event_create": [POINTER(c_void_p)],
     "wce_event_destroy": [c_void_p],
     "wce_event_record": [c_void_p, c_void_p],
+    "wce_event_query": [c_void_p],
     "wce_event_elapsed_ms": [POINTER(ctypes.c_float), c_void_p, c_void_p],
     "wce_last_error": [],
     "wce_version": [],
@@ -2011,6 +2012,13 @@ class Event:
     def record(self, stream=None):
         s = stream.handle if isinstance(stream, Stream) else stream
         _check(_lib.wce_event_record(self.handle, s), "wce_event_record")
+
+    def query(self) -> bool:
+        """wce_event_query: True once the work in front of the recorded event has completed; never waits."""
+        rc = _lib.wce_event_query(self.handle)
+        if rc < 0:
+            raise WceError(rc, "wce_event_query")
+        return rc == 1
 
     def elapsed_ms(self, end: "Event") -> float:
         ms = ctypes.c_float()

@@ -205,9 +205,23 @@ typedef struct {
  * share it; calls on the same stream are serialised (as the stream would).
  * Plans own their scratch.  wce_last_error() is per thread.
  *
+ * Every call that takes a `stream` -- the receive and transmit chain, the
+ * front end, wce_estimate and its kin, the conversions and the _async and
+ * device copies -- is ordered on that stream behind the work queued there
+ * before it and returns without waiting for it: it reads no device memory on
+ * the host and allocates nothing (wce_estimate: once the stream's scratch is
+ * sized, below).  A refused call (WCE_EINVAL) launches nothing.  Each call may
+ * run beside itself and beside every other on other streams, from one host
+ * thread or several, and gives the bytes of the same calls run one after
+ * another (tests/test_chain_streams_gpu.py); nothing orders two streams
+ * against each other but the host (wce_stream_synchronize, wce_event_query).
+ *
  * Pre-size that scratch for batches of up to n_frames so that wce_estimate
  * never allocates: _stream for one stream; wce_ctx_reserve for the NULL
- * stream, and as the minimum size of every stream's scratch created later.
+ * stream, and as the minimum size of every stream's scratch created later,
+ * by a call or by wce_ctx_reserve_stream.  Scratch that exists is only ever
+ * grown to the batch in hand or to the size asked for here, never to
+ * wce_ctx_reserve's: a reserved stream does not wait.
  * Without it the first larger batch on a stream allocates (synchronously on
  * that stream) and keeps the buffer until wce_ctx_destroy. */
 int wce_ctx_reserve(wce_ctx *ctx, int64_t n_frames);
@@ -1163,6 +1177,9 @@ int wce_stream_synchronize(void *stream);
 int wce_event_create(void **event);
 int wce_event_destroy(void *event);
 int wce_event_record(void *event, void *stream);
+/* 1: everything the stream held when the event was recorded has completed; 0: still pending (never waits);
+ * negative: an error code. */
+int wce_event_query(void *event);
 int wce_event_elapsed_ms(float *ms, void *start, void *stop);
 const char *wce_last_error(void);
 const char *wce_version(void);

@@ -90,7 +90,9 @@ int wce_debug_set_flat_chunk(long long frames);
  * kernels loop over frames: the front end's six builds, wce_front_end_sync,
  * wce_front_end_sync_stf, wce_short_field, wce_demodulate without evm and nerr, wce_soft_demap and _blocks,
  * wce_viterbi_decode, wce_reencode, wce_modulate, wce_channel, wce_transmit,
- * wce_psdu_frame, wce_psdu_deframe.
+ * wce_channel_tv, wce_transmit_tv, wce_combine, wce_sync_share,
+ * wce_psdu_frame, wce_psdu_deframe.  Each reads it on the host when it launches,
+ * so a kernel already queued keeps the grid it was launched with.
  * A frame's outputs depend on its own data alone, so 1 gives the bits of 0.
  * Ignored by wce_demodulate with evm or nerr and by wce_track_demodulate:
  * their kernels run one wave per frame with no loop, on a grid that covers the

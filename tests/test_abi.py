@@ -34,6 +34,8 @@ def test_library_exports_every_declared_symbol(wce):
     # the Python mirror binds the whole public ABI
     public = declared_symbols() - {s for s in syms if s.startswith("wce_debug")}
     assert public <= set(wce.wce.ABI), sorted(public - set(wce.wce.ABI))
+    assert "wce_event_query" in public and wce.wce.ABI["wce_event_query"] == [ctypes.c_void_p]
+    assert lib.wce_event_query.restype is ctypes.c_int and hasattr(wce.Event, "query")
 
 
 def test_version_string(wce):
