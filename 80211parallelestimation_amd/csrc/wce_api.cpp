@@ -375,15 +375,17 @@ static wce::LsArgs ls_args(const wce_frames *in, const wce_outputs *out, uint32_
     a.fs = in->frame_stride; a.bs = in->block_stride; a.ps = in->pre_stride; a.n = in->n_frames; a.blk = in->block;
     a.matlab = in->semantics == WCE_SEM_MATLAB;
     a.mask = mask & (WCE_EST_LS_ALL | WCE_EQUALIZE);
-    a.lt = reinterpret_cast<double *>(out->lt_ls);
-    a.lin = reinterpret_cast<double *>(out->ps_linear);
-    a.cub = reinterpret_cast<double *>(out->ps_cubic);
-    a.snc = reinterpret_cast<double *>(out->ps_sinc);
+    // an output whose bit the caller did not set is never written, whatever its pointer
+    // (the kernels store where (mask & bit) && pointer, and eq_src joins the mask below)
+    a.lt = (a.mask & WCE_EST_LT_LS) ? reinterpret_cast<double *>(out->lt_ls) : nullptr;
+    a.lin = (a.mask & WCE_EST_PS_LINEAR) ? reinterpret_cast<double *>(out->ps_linear) : nullptr;
+    a.cub = (a.mask & WCE_EST_PS_CUBIC) ? reinterpret_cast<double *>(out->ps_cubic) : nullptr;
+    a.snc = (a.mask & WCE_EST_PS_SINC) ? reinterpret_cast<double *>(out->ps_sinc) : nullptr;
     a.eq = reinterpret_cast<double *>(out->eq);
     a.os = out->out_stride; a.eqfs = out->eq_frame_stride; a.eqbs = out->eq_block_stride;
     a.eq_src = eq_src;
     a.f32 = (out->flags & WCE_OUT_LS_F32) != 0;
-    if (a.mask & WCE_EQUALIZE) a.mask |= eq_src;   // the blend needs that PS estimate
+    if (a.mask & WCE_EQUALIZE) a.mask |= eq_src;   // the blend needs that PS estimate (computed, not stored)
     return a;
 }
 

@@ -152,9 +152,11 @@ __device__ __forceinline__ void ls_store_rv(const LsArgs &a, int64_t f, int k, u
             // fades -- fp32 there is 7e-6 off), scaled by 2^-e, e the exponent of
             // the larger of |hlt|, |hps| (exact, and |H_UTIL|^2 stays inside fp32's
             // range), then rounded to fp32; rx_b is rounded to fp32 and scaled
-            // alike; rx / H_UTIL by v_rcp_f32 (1 ulp).  A numpy model of these
-            // roundings: <= 4.0e-7 norm-relative from the fp64 quotient over 40,000
-            // frames (G4 allows 1e-6; tests/test_config5_gpu.py checks it).
+            // alike; rx / H_UTIL by v_rcp_f32 (1 ulp).  tests/eq_model.py models
+            // these roundings operation for operation: its worst element is 2.8e-7
+            // from the long double quotient (tests/test_eq_model.py), fades
+            // included, and tests/test_equalize_gpu.py holds every element of every
+            // kernel that comes through here to twice that (G4 allows 1e-6).
             // WiFi_Equalization.m:3-8.
             const double2 dps = csub(hps, hlt);
             int e = 0;

@@ -176,8 +176,13 @@ typedef struct {
  *                   ignored), cubic divisors 14/28/42 (PS_Cubic.m:11-13). */
 enum { WCE_SEM_C = 0, WCE_SEM_MATLAB = 1 };
 
+/* An output is written if and only if its bit is in `mask`: lt_ls, ps_linear,
+ * ps_cubic, ps_sinc and ps_mmse by their WCE_EST_* bits, eq by WCE_EQUALIZE.  A
+ * buffer whose bit is not in `mask` is never written, whatever its pointer --
+ * one wce_outputs with every pointer set serves any mask -- and that holds for
+ * the eq_source estimate too, which WCE_EQUALIZE computes for its blend. */
 typedef struct {
-    wce_complex *lt_ls;         /* device [n_frames][out_stride], NULL = not requested */
+    wce_complex *lt_ls;         /* device [n_frames][out_stride]; may be NULL where its bit is not in mask */
     wce_complex *ps_linear;
     wce_complex *ps_cubic;
     wce_complex *ps_sinc;
@@ -186,16 +191,29 @@ typedef struct {
     int64_t out_stride;         /* >= 53 */
     int64_t eq_frame_stride;
     int64_t eq_block_stride;
-    uint32_t eq_source;         /* PS estimate blended with H_LT (WiFi_RX.m:60 uses PS_Linear);
-                                   0 = WCE_EST_PS_LINEAR */
+    uint32_t eq_source;         /* PS estimate blended with H_LT (WiFi_RX.m:60 uses PS_Linear): one of
+                                   WCE_EST_PS_LINEAR, WCE_EST_PS_CUBIC, WCE_EST_PS_SINC; 0 = WCE_EST_PS_LINEAR.
+                                   With WCE_EQUALIZE in mask any other value is WCE_EINVAL; without it the
+                                   field is not looked at.  The source need not be in mask */
     uint32_t flags;             /* WCE_OUT_* */
 } wce_outputs;
 
 /* wce_outputs.flags.  WCE_OUT_LS_F32: the LS family (lt_ls, ps_linear,
- * ps_cubic, ps_sinc) and eq are stored as complex float ({re, im} float, 8 B),
- * computed in fp64 and rounded once (BASELINE configs[4] "mixed fp64 solve /
- * fp32 interp"; <= 1e-7 relative).  ps_mmse stays complex double.  Strides
- * count elements of each buffer's own type. */
+ * ps_cubic, ps_sinc) and eq are stored as complex float ({re, im} float, 8 B)
+ * (BASELINE configs[4] "mixed fp64 solve / fp32 interp").  ps_mmse stays complex
+ * double.  Strides count elements of each buffer's own type.
+ *  - The LS family is computed in fp64 and rounded once (<= 1e-7 relative).
+ *  - eq divides in fp32: H_UTIL = wlt H_LT + wps H_PS is blended in fp64 (where
+ *    the two cancel, fp32 operands would lose the quotient), scaled by a power
+ *    of two and rounded to fp32; rx is rounded to fp32; the quotient is formed
+ *    in fp32 with v_rcp_f32.  Every element lies within 5.6e-7 of the exact
+ *    quotient, relative and by complex modulus, also where the blend cancels
+ *    down to 1e-6 of its terms (twice the worst element of the host model
+ *    tests/eq_model.py, 2.8e-7; tests/test_equalize_gpu.py checks each element).
+ *  - rx is rounded to fp32 before it is scaled, so under this flag each part of
+ *    rx must be 0 or lie in fp32's normal range (2^-126 <= |x| < 2^128) for that
+ *    bound to hold (checked with the channel, and rx with it, scaled by 2^100
+ *    and by 2^-100); inputs outside that range are not treated specially. */
 #define WCE_OUT_LS_F32 (1u << 0)
 
 /* Threading: one ctx may serve calls on several streams at once, from one
