@@ -92,7 +92,10 @@ __device__ __forceinline__ void dc_axis(double v, double w, double d, double inv
         const int opp = 2 * (int)((OPP[j] >> (3 * i)) & 7u) - (M - 1);
         const bool one = (g >> (NB - 1 - j)) & 1;
         const int dq = one ? own - opp : opp - own;            // q1 - q0
-        L[j] = (float)((w * ((double)dq * d)) * (2.0 * v - (double)(own + opp) * d));
+        // saturate, never overflow: a soft bit beyond float's range would leave as Inf and be read as an erasure
+        // by vt_llr, the most reliable bits of a strong frame first.  A NaN (Inf 0 of finite e and Hu) is a 0
+        const double s = (w * ((double)dq * d)) * (2.0 * v - (double)(own + opp) * d);
+        L[j] = s != s ? 0.0f : (float)fmin(fmax(s, -WCE_LLR_MAX), WCE_LLR_MAX);
     }
 }
 

@@ -1156,8 +1156,13 @@ __device__ __forceinline__ void exact_first_step(const SolveArgs &a, L &s, int64
     const double2 al = cscale(cmul(xl, uf), ac);
     const double2 be = cmul(wf, cconj(xl));
     // pivot: the largest |al_l|^2 (float key, lane in the low 6 bits; ties and
-    // the last few mantissa bits do not matter for the choice)
-    const float mag = (float)(al.x * al.x + al.y * al.y);
+    // the last few mantissa bits do not matter for the choice).  |al|^2 is taken relative to b's power of two:
+    // it carries the square of the received level, and as a bare float it was Inf or 0 on every lane from a
+    // level of about 2^+-64 on, which left the choice to the lane number; the scaling is exact, so at any level
+    // the keys order as they do at unit level (b = 0 or not finite: any exponent gives a valid pivot)
+    int eb = 0;
+    (void)frexp(bc, &eb);
+    const float mag = (float)ldexp(al.x * al.x + al.y * al.y, -eb);
     const uint32_t key = act ? ((__float_as_uint(mag) & ~63u) | (uint32_t)lane) : 0u;
     const int m = __builtin_amdgcn_readfirstlane((int)(wave_max_u32(key) & 63u));
     const double2 alm = readlane_c(al, m), bem = readlane_c(be, m);

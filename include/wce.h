@@ -693,7 +693,12 @@ int wce_track_demodulate(wce_ctx *ctx, const wce_frames *in, const wce_track *p,
  *                decision and is left out; scale by 1 / ow2[f] for true LLRs.  If e or Hu is not
  *                finite every bit of that symbol gets L = 0, an erasure (the NaN row of an
  *                undetected packet decodes from all-zero LLRs).  fp64 arithmetic, rounded once to
- *                float.  Output in DEINTERLEAVED coded order:
+ *                float.  A soft bit of finite e and Hu is clamped to +-WCE_LLR_MAX = 2^100, so that
+ *                a strong signal saturates and never leaves float's range to be read as an erasure;
+ *                the decoder then cannot overflow either: 2 x 3240 x 2^100 < 2^128.
+ *                Signal level: Hu times g = 2^k multiplies every unclamped soft bit by g^2, and so do
+ *                eq and scale both times g, bit for bit while the soft bits stay normal floats.
+ *                Output in DEINTERLEAVED coded order:
  *                llr[f*llr_frame_stride + b*llr_block_stride + k], k < N_CBPS.
  *   decoder      (wce_viterbi_decode) maximum-correlation Viterbi over the depunctured stream,
  *                float metrics, pm_0[0] = 0, pm_0[s != 0] = -inf.  Per step, with the pair
@@ -729,6 +734,7 @@ int wce_track_demodulate(wce_ctx *ctx, const wce_frames *in, const wce_track *p,
  *  - wce_decode_info_bits: T for a modulation and rate, or WCE_EINVAL. */
 enum { WCE_RATE_1_2 = 0, WCE_RATE_2_3 = 1, WCE_RATE_3_4 = 2 };
 #define WCE_DEC_TERMINATED (1u << 0)   /* trace back from state 0 */
+#define WCE_LLR_MAX 1267650600228229401496703205376.0   /* 2^100: the largest magnitude of a soft bit */
 
 int wce_soft_demap(wce_ctx *ctx, const wce_complex *eq, int64_t eq_frame_stride, int64_t eq_block_stride,
                    const wce_demod *p, int64_t n_frames, float *llr, int64_t llr_frame_stride,
@@ -1108,6 +1114,31 @@ typedef struct {              /* each pointer may be NULL = not wanted; not both
 int wce_combine(wce_ctx *ctx, const wce_combine_par *p, int64_t n_frames, const wce_combine_out *out, void *stream);
 int wce_sync_share(wce_ctx *ctx, int32_t n_branches, int64_t branch_stride, int64_t n_packets, const double *metric,
                    int32_t *start, double *cfo, void *stream);
+
+/* ---- Signal level: what a gain g does to every call ----
+ * A capture arrives at whatever level the ADC and the AGC give, and two antennas run two
+ * AGCs.  No call has a constant with units, an absolute threshold or an absolute guard:
+ * multiplying its inputs by g multiplies its outputs by the power of g its definition
+ * carries and changes nothing else.  For g = 2^k that holds bit for bit (integers: equal)
+ * while nothing overflows or goes subnormal; tests/gain_model.py is the table and the tests
+ * hold it at 2^+-11 and 2^+-40, and at 2^+-100 where every output is fp64.
+ *  - wce_front_end_blocks*:  samples g -> sym g.   wce_front_end_preamble*:  lptot g ->
+ *    pre_fft g, ow2 g^2, the estimated cfo unchanged.
+ *  - wce_front_end_sync, _sync_stf:  capture g, or ltf g -> start, cfo and the metrics unchanged.
+ *  - wce_estimate, wce_estimate_noise, every estimator and route.  The channel's gain: rx g,
+ *    the frames' rx_pre g, the context's rx_pre g and ow2 g^2 (per-frame ow2 g^2, Rhh g^2) ->
+ *    every estimate g, eq unchanged.  The transmitter's convention: tx g, tx_pre g (Rhh / g^2,
+ *    the constant-modulus pattern g) -> every estimate / g, eq g.
+ *  - wce_demodulate, wce_track_demodulate:  rx g, h g, h_lt g -> eq, sym, theta, evm, nerr
+ *    unchanged, h_blocks g, h_last g.  tx g, rx g, scale g -> eq g, everything else unchanged.
+ *  - wce_soft_demap, _blocks:  h g (hb g), or eq g and scale g -> llr g^2, up to the clamp.
+ *    wce_viterbi_decode:  llr g -> bits and nbiterr unchanged.
+ *  - wce_reencode:  rx g -> h g, tx unchanged.  scale g (and the pilots g) -> tx g, h / g.
+ *  - wce_combine with ow2: each branch its own gain, rx_a g_a, h_a g_a, ow2_a g_a^2 -> rx_c and
+ *    h_c unchanged.  Without: one gain for all, rx_c g and h_c g.
+ *  - wce_modulate:  sym g, tx_pre g -> wave g.   wce_channel, wce_transmit and the _tv pair:
+ *    taps g (knots g), or the wave (the symbols and tx_pre) g, with ow2 g^2 -> capture g.
+ *    wce_short_field:  amplitude g -> wave g. */
 
 /* Non-finite guard.  The reference passes NaN/Inf through
  * silently: main.c's PS_MMSE returns NaN x 53 (main.c:148-212), a zero pilot

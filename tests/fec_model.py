@@ -11,7 +11,8 @@ decoder; the definitions are the ones in include/wce.h (IEEE 802.11-2020
     mapping      transmitted bit j: data subcarrier floor(j/bpsc), bit j mod bpsc, b0 first; the first bpsc/2
                  bits give the I level, the rest the Q level, by 802.11's Gray tables
     soft bit     L = |Hu|^2 (D0 - D1), D_c = min over the axis levels whose label bit is c of (v - level)^2;
-                 0 for every bit of a symbol whose e or Hu is not finite; in deinterleaved coded order
+                 0 for every bit of a symbol whose e or Hu is not finite, else clamped to +-LLR_MAX = 2^100;
+                 in deinterleaved coded order
     decoder      maximum-correlation Viterbi over the depunctured stream (0 at the punctured places), 64
                  states, p0 wins a tie, no renormalisation
 
@@ -36,6 +37,7 @@ TAPS_B = (0, 1, 2, 3, 6)      # 171 octal = 1111001
 # bound (c) of the GPU tests, derived and checked in tests/test_decode_abi.py:
 # |L_dev - L_ld| <= 2^-23 |L_ld| + TOL_ABS max |L_ld| of the frame
 TOL_ABS = 1e-13
+LLR_MAX = 2.0 ** 100          # WCE_LLR_MAX: a finite soft bit saturates there
 # SNR of the integer set per bits per subcarrier (BPSK rate 1/2 runs at INT_SNR_BPSK_1_2: at 6 dB one frame
 # of its 67 decodes with errors, at 2 dB 19 do)
 INT_SNR = {1: 6.0, 2: 9.0, 4: 14.0, 6: 19.0}
@@ -167,6 +169,7 @@ def llr(eq, hu, mod, scale=dm.SCALE, real=LD):
                 d0 = np.min(np.where(one, np.inf, dist), axis=-1)
                 d1 = np.min(np.where(one, dist, np.inf), axis=-1)
                 out[..., ax * nax + j] = w * (d0 - d1)
+        out = np.where(np.isnan(out), real(0), np.clip(out, real(-LLR_MAX), real(LLR_MAX)))   # saturate
         out = np.where(ok[..., None], out, real(0))
     txorder = out.reshape(e.shape[0], NBLK, n_cbps(mod))
     return txorder[:, :, interleave_index(mod)]
