@@ -1,5 +1,6 @@
-// wce_api.cpp -- C ABI (include/wce.h): context lifetime, argument checks,
-// launches, and thin HIP runtime helpers.
+// wce_api.cpp -- C ABI (include/wce.h): context lifetime, the estimator's argument
+// checks and launches, plans, workspaces, and thin HIP runtime helpers.  The receive
+// and transmit chain's calls are in wce_chain_api.cpp.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -11,7 +12,7 @@
 #include <string>
 #include <vector>
 
-#include "wce_internal.h"
+#include "wce_api_check.h"
 
 using wce::State;
 
@@ -57,12 +58,6 @@ static thread_local std::string g_err;
 // mmse_rank1_kernel's PLAIN build may run: X is the whole tx block and a = 1 (wce_state.cpp, TEXTBOOK)
 static bool state_r1_plain(const State *st) { return st->acoef == 1.0 && st->xmask == (1ull << wce::NSC) - 1; }
 
-static int fail(int code, const char *what)
-{
-    g_err = what;
-    return code;
-}
-
 static int hipfail(hipError_t e, const char *what)
 {
     g_err = std::string(what) + ": " + hipGetErrorString(e);
@@ -86,22 +81,6 @@ static int check_device(int device)
         return fail(WCE_ENODEV, "libwce is built for gfx950 (MI355X) only");
     return WCE_OK;
 }
-
-namespace {
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int d)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != d) (void)hipSetDevice(d);
-    }
-    ~DeviceGuard()
-    {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-}  // namespace
 
 extern "C" {
 
@@ -468,7 +447,7 @@ static int ldc_convert(const void *src, void *dst, int64_t n, bool to_complex, v
     if (n == 0) return WCE_OK;
     if (n > (int64_t)0x7fffffff * 256) return fail(WCE_EINVAL, "n too large for one launch");   // also keeps n * 32 in range
     if (!src || !dst) return fail(WCE_EINVAL, "null src/dst");
-    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15)
+    if (misaligned(src, 16) || misaligned(dst, 16))
         return fail(WCE_EINVAL, "src/dst not 16-byte aligned");   // 16-B vector loads and stores
     const char *a = static_cast<const char *>(src), *b = static_cast<const char *>(dst);
     const int64_t sb = n * (to_complex ? 32 : 16), db = n * (to_complex ? 16 : 32);
@@ -861,877 +840,6 @@ int wce_synth_frames(wce_ctx *c, wce_complex *tx, wce_complex *rx, wce_complex *
     return rc ? fail(rc, "synth launch") : WCE_OK;
 }
 
-// ---------------------------------------------------------------- front end
-// the _at calls' window: start[] and capture_len (win); at == false: neither is looked at
-static int check_window(bool at, const int32_t *start, int64_t win, int64_t stride)
-{
-    if (!at) return WCE_OK;
-    if (!start) return fail(WCE_EINVAL, "null start");
-    if (reinterpret_cast<uintptr_t>(start) % 4) return fail(WCE_EINVAL, "start not 4-byte aligned");
-    if (win < 2 * WCE_FFT_SIZE || win >= (int64_t)1 << 31) return fail(WCE_EINVAL, "capture_len outside [128, 2^31)");
-    if (stride < win) return fail(WCE_EINVAL, "capture_stride < capture_len");
-    return WCE_OK;
-}
-
-// cfo == null: the plain build (sample_offset is not looked at).  at: the per-frame-start build, frame f's
-// packet at samples[f*packet_stride + start[f] + 128 + sample_offset] of a window of win samples
-static int front_blocks(wce_ctx *c, const wce_complex *samples, int64_t packet_stride, int64_t n_frames,
-                        int32_t n_blocks, const double *cfo, int64_t sample_offset, wce_complex *sym,
-                        int64_t frame_stride, int64_t block_stride, void *stream, bool at = false,
-                        const int32_t *start = nullptr, int64_t win = 0)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (n_frames < 0 || n_blocks < 1) return fail(WCE_EINVAL, "n_frames < 0 or n_blocks < 1");
-    if (n_frames == 0) return WCE_OK;
-    if (!samples || !sym) return fail(WCE_EINVAL, "null buffer");
-    if (int rc = check_window(at, start, win, packet_stride)) return rc;
-    if (!at && packet_stride < (int64_t)n_blocks * WCE_SAMPLES_PER_BLOCK)
-        return fail(WCE_EINVAL, "packet_stride < 80 n_blocks");
-    if (block_stride < wce::NSC || frame_stride < (int64_t)(n_blocks - 1) * block_stride + wce::NSC)
-        return fail(WCE_EINVAL, "output strides too small");
-    if (n_frames * n_blocks >= (int64_t)1 << 31) return fail(WCE_EINVAL, "n_frames * n_blocks >= 2^31");
-    if (cfo || at) {
-        if (reinterpret_cast<uintptr_t>(cfo) % 8) return fail(WCE_EINVAL, "cfo not 8-byte aligned");
-        if (sample_offset >= (int64_t)1 << 31 || sample_offset <= -((int64_t)1 << 31))
-            return fail(WCE_EINVAL, "|sample_offset| >= 2^31");
-    }
-    wce::FrontArgs a{};
-    a.src = reinterpret_cast<const double *>(samples);
-    a.dst = reinterpret_cast<double *>(sym);
-    a.ps = packet_stride; a.off = WCE_SAMPLES_PER_BLOCK - WCE_FFT_SIZE; a.fs = frame_stride; a.bs = block_stride;
-    a.n_units = (uint32_t)(n_frames * n_blocks); a.nb = (uint32_t)n_blocks;
-    a.cfo = const_cast<double *>(cfo);   // est = 0: read only
-    a.n0 = cfo ? sample_offset + a.off : 0;
-    if (at) {   // the packet follows the 128-sample field; the time axis (n0) is the CFO call's
-        a.n0 = sample_offset + a.off;
-        a.off += 2 * WCE_FFT_SIZE + sample_offset;
-        a.start = start; a.win = win;
-        a.span = (int64_t)(n_blocks - 1) * WCE_SAMPLES_PER_BLOCK + WCE_FFT_SIZE;
-    }
-    DeviceGuard g(c->device);
-    int rc = wce::launch_front(a, false, stream);
-    return rc ? fail(rc, "front end launch") : WCE_OK;
-}
-
-int wce_front_end_blocks(wce_ctx *c, const wce_complex *samples, int64_t packet_stride, int64_t n_frames,
-                         int32_t n_blocks, wce_complex *sym, int64_t frame_stride, int64_t block_stride,
-                         void *stream)
-{
-    return front_blocks(c, samples, packet_stride, n_frames, n_blocks, nullptr, 0, sym, frame_stride, block_stride,
-                        stream);
-}
-
-int wce_front_end_blocks_cfo(wce_ctx *c, const wce_complex *samples, int64_t packet_stride, int64_t n_frames,
-                             int32_t n_blocks, const double *cfo, int64_t sample_offset, wce_complex *sym,
-                             int64_t frame_stride, int64_t block_stride, void *stream)
-{
-    return front_blocks(c, samples, packet_stride, n_frames, n_blocks, cfo, sample_offset, sym, frame_stride,
-                        block_stride, stream);
-}
-
-// cfo == null: the plain build.  start != null: the per-frame-start build, lptot the capture windows of
-// lptot_len samples, frame f's field at lptot[f*lptot_stride + start[f] + (0..127)]
-static int front_preamble(wce_ctx *c, const wce_complex *lptot, int64_t lptot_stride, int64_t lptot_len,
-                          int64_t n_frames, wce_complex *pre_fft, int64_t pre_stride, double *ow2, double *cfo,
-                          int estimate, void *stream, bool at = false, const int32_t *start = nullptr)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (n_frames < 0) return fail(WCE_EINVAL, "n_frames < 0");
-    if (n_frames == 0) return WCE_OK;
-    if (!lptot || !pre_fft) return fail(WCE_EINVAL, "null buffer");
-    if (int rc = check_window(at, start, lptot_len, lptot_stride)) return rc;
-    if (at && estimate && !cfo) return fail(WCE_EINVAL, "estimate without cfo");
-    if (lptot_len < 2 * WCE_FFT_SIZE || lptot_stride < lptot_len) return fail(WCE_EINVAL, "lptot_len < 128 or stride < len");
-    if (pre_stride < wce::NSC) return fail(WCE_EINVAL, "pre_stride < 53");
-    if (n_frames >= (int64_t)1 << 31) return fail(WCE_EINVAL, "n_frames >= 2^31");
-    if (reinterpret_cast<uintptr_t>(cfo) % 8) return fail(WCE_EINVAL, "cfo not 8-byte aligned");
-    wce::FrontArgs a{};
-    a.src = reinterpret_cast<const double *>(lptot);
-    a.dst = reinterpret_cast<double *>(pre_fft);
-    a.ow2 = ow2;
-    a.ps = lptot_stride; a.off = lptot_len - 2 * WCE_FFT_SIZE; a.fs = pre_stride; a.bs = 0;
-    a.n_units = (uint32_t)n_frames; a.nb = 1;
-    a.cfo = cfo;
-    a.n0 = -2 * WCE_FFT_SIZE;   // the long training field ends at n = 0
-    a.est = cfo && estimate;
-    if (at) { a.off = 0; a.start = start; a.win = lptot_len; a.span = 2 * WCE_FFT_SIZE; }
-    DeviceGuard g(c->device);
-    int rc = wce::launch_front(a, true, stream);
-    return rc ? fail(rc, "front end launch") : WCE_OK;
-}
-
-int wce_front_end_preamble(wce_ctx *c, const wce_complex *lptot, int64_t lptot_stride, int64_t lptot_len,
-                           int64_t n_frames, wce_complex *pre_fft, int64_t pre_stride, double *ow2, void *stream)
-{
-    return front_preamble(c, lptot, lptot_stride, lptot_len, n_frames, pre_fft, pre_stride, ow2, nullptr, 0, stream);
-}
-
-int wce_front_end_preamble_cfo(wce_ctx *c, const wce_complex *lptot, int64_t lptot_stride, int64_t lptot_len,
-                               int64_t n_frames, wce_complex *pre_fft, int64_t pre_stride, double *ow2, double *cfo,
-                               int estimate, void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (!cfo) return fail(WCE_EINVAL, "null cfo");
-    return front_preamble(c, lptot, lptot_stride, lptot_len, n_frames, pre_fft, pre_stride, ow2, cfo, estimate,
-                          stream);
-}
-
-int wce_front_end_preamble_at(wce_ctx *c, const wce_complex *capture, int64_t capture_stride, int64_t capture_len,
-                              int64_t n_frames, const int32_t *start, wce_complex *pre_fft, int64_t pre_stride,
-                              double *ow2, double *cfo, int estimate, void *stream)
-{
-    return front_preamble(c, capture, capture_stride, capture_len, n_frames, pre_fft, pre_stride, ow2, cfo, estimate,
-                          stream, true, start);
-}
-
-int wce_front_end_blocks_at(wce_ctx *c, const wce_complex *capture, int64_t capture_stride, int64_t capture_len,
-                            int64_t n_frames, int32_t n_blocks, const int32_t *start, const double *cfo,
-                            int64_t sample_offset, wce_complex *sym, int64_t frame_stride, int64_t block_stride,
-                            void *stream)
-{
-    return front_blocks(c, capture, capture_stride, n_frames, n_blocks, cfo, sample_offset, sym, frame_stride,
-                        block_stride, stream, true, start, capture_len);
-}
-
-int wce_front_end_sync(wce_ctx *c, const wce_complex *capture, int64_t capture_stride, int64_t capture_len,
-                       int64_t n_frames, const wce_complex *ltf, double threshold, int32_t backoff, int32_t *start,
-                       double *metric, void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (n_frames < 0) return fail(WCE_EINVAL, "n_frames < 0");
-    if (capture_len < 2 * WCE_FFT_SIZE || capture_len >= (int64_t)1 << 31)
-        return fail(WCE_EINVAL, "capture_len outside [128, 2^31)");
-    if (capture_stride < capture_len) return fail(WCE_EINVAL, "capture_stride < capture_len");
-    if (!(threshold >= 0.0 && threshold <= 1.0)) return fail(WCE_EINVAL, "threshold outside [0, 1]");
-    if (backoff < 0 || backoff > 31) return fail(WCE_EINVAL, "backoff outside [0, 31]");
-    if (!start || reinterpret_cast<uintptr_t>(start) % 4) return fail(WCE_EINVAL, "start null or not 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(metric) % 8) return fail(WCE_EINVAL, "metric not 8-byte aligned");
-    if (!ltf || reinterpret_cast<uintptr_t>(ltf) % 16) return fail(WCE_EINVAL, "ltf null or not 16-byte aligned");
-    if (!capture || reinterpret_cast<uintptr_t>(capture) % 16)
-        return fail(WCE_EINVAL, "capture null or not 16-byte aligned");
-    if (n_frames == 0) return WCE_OK;
-    wce::SyncArgs a{};
-    a.capture = reinterpret_cast<const double *>(capture);
-    a.ltf = reinterpret_cast<const double *>(ltf);
-    a.stride = capture_stride; a.len = capture_len; a.n = n_frames;
-    a.threshold = threshold; a.backoff = backoff;
-    a.start = start; a.metric = metric;
-    DeviceGuard g(c->device);
-    int rc = wce::launch_sync(a, c->cus, stream);
-    return rc ? fail(rc, "sync launch") : WCE_OK;
-}
-
-int wce_front_end_sync_stf(wce_ctx *c, const wce_complex *capture, int64_t capture_stride, int64_t capture_len,
-                           int64_t n_frames, const wce_complex *ltf, double threshold_stf, double threshold_ltf,
-                           int32_t backoff, int32_t *start, double *cfo, double *metric_stf, double *metric_ltf,
-                           void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (n_frames < 0) return fail(WCE_EINVAL, "n_frames < 0");
-    if (capture_len < 2 * WCE_FFT_SIZE + 16 || capture_len >= (int64_t)1 << 31)
-        return fail(WCE_EINVAL, "capture_len outside [144, 2^31)");
-    if (capture_stride < capture_len) return fail(WCE_EINVAL, "capture_stride < capture_len");
-    if (!(threshold_stf >= 0.0 && threshold_stf <= 1.0)) return fail(WCE_EINVAL, "threshold_stf outside [0, 1]");
-    if (!(threshold_ltf >= 0.0 && threshold_ltf <= 1.0)) return fail(WCE_EINVAL, "threshold_ltf outside [0, 1]");
-    if (backoff < 0 || backoff > 31) return fail(WCE_EINVAL, "backoff outside [0, 31]");
-    if (!start || reinterpret_cast<uintptr_t>(start) % 4) return fail(WCE_EINVAL, "start null or not 4-byte aligned");
-    if (!cfo || reinterpret_cast<uintptr_t>(cfo) % 8) return fail(WCE_EINVAL, "cfo null or not 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(metric_stf) % 8 || reinterpret_cast<uintptr_t>(metric_ltf) % 8)
-        return fail(WCE_EINVAL, "metric not 8-byte aligned");
-    if (!ltf || reinterpret_cast<uintptr_t>(ltf) % 16) return fail(WCE_EINVAL, "ltf null or not 16-byte aligned");
-    if (!capture || reinterpret_cast<uintptr_t>(capture) % 16)
-        return fail(WCE_EINVAL, "capture null or not 16-byte aligned");
-    if (n_frames == 0) return WCE_OK;
-    wce::SyncStfArgs a{};
-    a.capture = reinterpret_cast<const double *>(capture);
-    a.ltf = reinterpret_cast<const double *>(ltf);
-    a.stride = capture_stride; a.len = capture_len; a.n = n_frames;
-    a.threshold_stf = threshold_stf; a.threshold_ltf = threshold_ltf; a.backoff = backoff;
-    a.start = start; a.cfo = cfo; a.metric_stf = metric_stf; a.metric_ltf = metric_ltf;
-    DeviceGuard g(c->device);
-    int rc = wce::launch_sync_stf(a, c->cus, stream);
-    return rc ? fail(rc, "sync_stf launch") : WCE_OK;
-}
-
-int wce_short_field(wce_ctx *c, double amplitude, wce_complex *wave, int64_t wave_stride, int64_t n_frames,
-                    void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (n_frames < 0) return fail(WCE_EINVAL, "n_frames < 0");
-    if (!wave || reinterpret_cast<uintptr_t>(wave) % 16) return fail(WCE_EINVAL, "wave null or not 16-byte aligned");
-    if (wave_stride < wce::SHORT_FIELD_LEN) return fail(WCE_EINVAL, "wave_stride < 160");
-    if (!std::isfinite(amplitude)) return fail(WCE_EINVAL, "amplitude not finite");
-    if (n_frames == 0) return WCE_OK;
-    wce::ShortFieldArgs a{};
-    a.wave = reinterpret_cast<double *>(wave);
-    a.stride = wave_stride; a.n = n_frames; a.amplitude = amplitude;
-    wce::short_field_period(a.t);
-    DeviceGuard g(c->device);
-    int rc = wce::launch_short_field(a, c->cus, stream);
-    return rc ? fail(rc, "short field launch") : WCE_OK;
-}
-
-// ---------------------------------------------------------------- demodulation
-int wce_demodulate(wce_ctx *c, const wce_frames *in, const wce_demod *p, const wce_demod_out *out, void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (!in || !p || !out) return fail(WCE_EINVAL, "wce_demodulate: null frames, parameters or outputs");
-    if (!in->tx || !in->rx) return fail(WCE_EINVAL, "wce_demodulate: tx/rx required");
-    if (!p->h) return fail(WCE_EINVAL, "wce_demodulate: h required");
-    if (!out->eq && !out->sym && !out->theta && !out->evm && !out->nerr)
-        return fail(WCE_EINVAL, "wce_demodulate: no output requested");
-    if (p->h_stride < wce::NSC) return fail(WCE_EINVAL, "wce_demodulate: h_stride < 53");
-    double K;
-    switch (p->modulation) {   // the doubles nearest to 1 / sqrt(1, 2, 10, 42)
-    case WCE_MOD_BPSK: K = 1.0; break;
-    case WCE_MOD_QPSK: K = 0.70710678118654752440; break;
-    case WCE_MOD_QAM16: K = 0.31622776601683793320; break;
-    case WCE_MOD_QAM64: K = 0.15430334996209191026; break;
-    default: return fail(WCE_EINVAL, "wce_demodulate: unknown modulation");
-    }
-    if (p->flags & ~(WCE_DEMOD_TRACK | WCE_DEMOD_REF_TX)) return fail(WCE_EINVAL, "wce_demodulate: unknown flag bits");
-    if (!(p->scale > 0.0) || p->scale * 0.0 != 0.0) return fail(WCE_EINVAL, "wce_demodulate: scale not positive and finite");
-    // the frames: the fields the call reads (block, semantics and the preambles are ignored)
-    wce_frames fr = *in;
-    fr.rx_pre = fr.tx_pre = nullptr;
-    fr.block = 0;
-    fr.semantics = WCE_SEM_C;
-    int rc = check_frames(&fr, true);
-    if (rc) return rc;
-    const int64_t n = in->n_frames;
-    const int64_t span = (wce::NBLK - 1);
-    if (out->eq && (out->eq_block_stride < wce::NSC ||
-                    (n > 1 && out->eq_frame_stride < span * out->eq_block_stride + wce::NSC)))
-        return fail(WCE_EINVAL, "wce_demodulate: eq strides too small");
-    if (out->sym && (out->sym_block_stride < wce::NSC ||
-                     (n > 1 && out->sym_frame_stride < span * out->sym_block_stride + wce::NSC)))
-        return fail(WCE_EINVAL, "wce_demodulate: sym strides too small");
-    if (reinterpret_cast<uintptr_t>(out->theta) % 8 || reinterpret_cast<uintptr_t>(out->evm) % 8)
-        return fail(WCE_EINVAL, "wce_demodulate: theta or evm not 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(out->nerr) % 4) return fail(WCE_EINVAL, "wce_demodulate: nerr not 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(p->h) % 16 || reinterpret_cast<uintptr_t>(p->h_lt) % 16 ||
-        reinterpret_cast<uintptr_t>(out->eq) % 16)
-        return fail(WCE_EINVAL, "wce_demodulate: h, h_lt or eq not 16-byte aligned");
-    if (n == 0) return WCE_OK;
-    wce::DemodArgs a{};
-    a.tx = reinterpret_cast<const double *>(in->tx);
-    a.rx = reinterpret_cast<const double *>(in->rx);
-    a.h = reinterpret_cast<const double *>(p->h);
-    a.hlt = reinterpret_cast<const double *>(p->h_lt);
-    a.fs = in->frame_stride; a.bs = in->block_stride; a.hs = p->h_stride; a.n = n;
-    a.mod = p->modulation; a.flags = p->flags;
-    a.scale = p->scale; a.d = p->scale * K;
-    a.eq = reinterpret_cast<double *>(out->eq);
-    a.sym = out->sym; a.theta = out->theta; a.evm = out->evm; a.nerr = out->nerr;
-    a.eqfs = out->eq_frame_stride; a.eqbs = out->eq_block_stride;
-    a.symfs = out->sym_frame_stride; a.symbs = out->sym_block_stride;
-    DeviceGuard g(c->device);
-    rc = wce::launch_demod(a, stream);
-    return rc ? fail(rc, "demod launch") : WCE_OK;
-}
-
-// the doubles nearest to 1 / sqrt(1, 2, 10, 42), as wce_demodulate; 0 for an unknown modulation
-static double mod_K(int32_t modulation)
-{
-    switch (modulation) {
-    case WCE_MOD_BPSK: return 1.0;
-    case WCE_MOD_QPSK: return 0.70710678118654752440;
-    case WCE_MOD_QAM16: return 0.31622776601683793320;
-    case WCE_MOD_QAM64: return 0.15430334996209191026;
-    default: return 0.0;
-    }
-}
-
-// ---------------------------------------------------------------- per-block tracking
-int wce_track_demodulate(wce_ctx *c, const wce_frames *in, const wce_track *p, const wce_track_out *out, void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (!in || !p || !out) return fail(WCE_EINVAL, "wce_track_demodulate: null frames, parameters or outputs");
-    if (!in->tx || !in->rx) return fail(WCE_EINVAL, "wce_track_demodulate: tx/rx required");
-    if (!p->h) return fail(WCE_EINVAL, "wce_track_demodulate: h required");
-    if (!out->eq && !out->sym && !out->theta && !out->evm && !out->nerr && !out->h_blocks && !out->h_last)
-        return fail(WCE_EINVAL, "wce_track_demodulate: no output requested");
-    if (p->h_stride < wce::NSC) return fail(WCE_EINVAL, "wce_track_demodulate: h_stride < 53");
-    const double K = mod_K(p->modulation);
-    if (K == 0.0) return fail(WCE_EINVAL, "wce_track_demodulate: unknown modulation");
-    if (p->flags & ~(WCE_TRACK_PHASE | WCE_TRACK_REF_TX | WCE_TRACK_KNOWN_TX))
-        return fail(WCE_EINVAL, "wce_track_demodulate: unknown flag bits");
-    if (!(p->scale > 0.0) || p->scale * 0.0 != 0.0)
-        return fail(WCE_EINVAL, "wce_track_demodulate: scale not positive and finite");
-    if (!(p->mu >= 0.0 && p->mu <= 1.0)) return fail(WCE_EINVAL, "wce_track_demodulate: mu outside [0, 1]");
-    if (p->beta < 0 || p->beta > 4) return fail(WCE_EINVAL, "wce_track_demodulate: beta outside 0..4");
-    // the frames: the fields the call reads (block, semantics and the preambles are ignored)
-    wce_frames fr = *in;
-    fr.rx_pre = fr.tx_pre = nullptr;
-    fr.block = 0;
-    fr.semantics = WCE_SEM_C;
-    int rc = check_frames(&fr, true);
-    if (rc) return rc;
-    const int64_t n = in->n_frames;
-    const int64_t span = (wce::NBLK - 1);
-    if (out->eq && (out->eq_block_stride < wce::NSC ||
-                    (n > 1 && out->eq_frame_stride < span * out->eq_block_stride + wce::NSC)))
-        return fail(WCE_EINVAL, "wce_track_demodulate: eq strides too small");
-    if (out->sym && (out->sym_block_stride < wce::NSC ||
-                     (n > 1 && out->sym_frame_stride < span * out->sym_block_stride + wce::NSC)))
-        return fail(WCE_EINVAL, "wce_track_demodulate: sym strides too small");
-    if (out->h_blocks && (out->hb_block_stride < wce::NSC ||
-                          (n > 1 && out->hb_frame_stride < span * out->hb_block_stride + wce::NSC)))
-        return fail(WCE_EINVAL, "wce_track_demodulate: h_blocks strides too small");
-    if (out->h_last && out->h_last_stride < wce::NSC) return fail(WCE_EINVAL, "wce_track_demodulate: h_last_stride < 53");
-    if (reinterpret_cast<uintptr_t>(out->theta) % 8 || reinterpret_cast<uintptr_t>(out->evm) % 8)
-        return fail(WCE_EINVAL, "wce_track_demodulate: theta or evm not 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(out->nerr) % 4)
-        return fail(WCE_EINVAL, "wce_track_demodulate: nerr not 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(p->h) % 16 || reinterpret_cast<uintptr_t>(out->eq) % 16)
-        return fail(WCE_EINVAL, "wce_track_demodulate: h or eq not 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(out->h_blocks) % 16 || reinterpret_cast<uintptr_t>(out->h_last) % 16)
-        return fail(WCE_EINVAL, "wce_track_demodulate: h_blocks or h_last not 16-byte aligned");
-    if (n == 0) return WCE_OK;
-    wce::TrackArgs a{};
-    a.tx = reinterpret_cast<const double *>(in->tx);
-    a.rx = reinterpret_cast<const double *>(in->rx);
-    a.h = reinterpret_cast<const double *>(p->h);
-    a.fs = in->frame_stride; a.bs = in->block_stride; a.hs = p->h_stride; a.n = n;
-    a.mod = p->modulation; a.flags = p->flags;
-    a.scale = p->scale; a.d = p->scale * K;
-    a.mu = p->mu; a.beta = p->beta;
-    a.eq = reinterpret_cast<double *>(out->eq);
-    a.sym = out->sym; a.theta = out->theta; a.evm = out->evm; a.nerr = out->nerr;
-    a.eqfs = out->eq_frame_stride; a.eqbs = out->eq_block_stride;
-    a.symfs = out->sym_frame_stride; a.symbs = out->sym_block_stride;
-    a.hb = reinterpret_cast<double *>(out->h_blocks);
-    a.hbfs = out->hb_frame_stride; a.hbbs = out->hb_block_stride;
-    a.hl = reinterpret_cast<double *>(out->h_last);
-    a.hls = out->h_last_stride;
-    DeviceGuard g(c->device);
-    rc = wce::launch_track(a, stream);
-    return rc ? fail(rc, "track launch") : WCE_OK;
-}
-
-// ---------------------------------------------------------------- receive diversity
-static bool strides_hold(int64_t n, int64_t fs, int64_t bs, int64_t row);
-
-// A branches of stride s on top of frames [n][15][53] of strides fs / bs: no two branches share an element where
-// the branch stride spans a whole branch, or fits the branches inside a block stride, or between frame and block.
-// 128-bit products: the strides are the caller's
-static bool branches_apart(int64_t A, int64_t s, int64_t n, int64_t fs, int64_t bs)
-{
-    typedef __int128 i128;
-    if (A <= 1) return true;
-    if (s < wce::NSC) return false;
-    const i128 blocks = (i128)(wce::NBLK - 1) * bs + wce::NSC, all = (i128)(A - 1) * s;
-    if ((i128)s >= (i128)(n > 1 ? n - 1 : 0) * fs + blocks) return true;
-    if (all + wce::NSC <= (i128)bs) return true;
-    return (i128)s >= blocks && all + blocks <= (i128)fs;
-}
-// the same for rows [n][53] of stride hs
-static bool rows_apart(int64_t A, int64_t s, int64_t n, int64_t hs)
-{
-    typedef __int128 i128;
-    if (A <= 1) return true;
-    if (s < wce::NSC) return false;
-    if ((i128)s >= (i128)(n > 1 ? n - 1 : 0) * hs + wce::NSC) return true;
-    return (i128)(A - 1) * s + wce::NSC <= (i128)hs;
-}
-
-int wce_combine(wce_ctx *c, const wce_combine_par *p, int64_t n_frames, const wce_combine_out *out, void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (!p || !out) return fail(WCE_EINVAL, "wce_combine: null parameters or outputs");
-    if (!p->rx || !p->h) return fail(WCE_EINVAL, "wce_combine: rx and h required");
-    if (!out->rx && !out->h) return fail(WCE_EINVAL, "wce_combine: no output requested");
-    const int64_t A = p->n_branches, n = n_frames;
-    if (A < 1 || A > WCE_COMBINE_MAX_BRANCHES) return fail(WCE_EINVAL, "wce_combine: n_branches outside 1..8");
-    if (n < 0 || n > 0x7fffffffll) return fail(WCE_EINVAL, "wce_combine: n_frames < 0 or > 2^31 - 1");
-    if (!strides_hold(n, p->rx_frame_stride, p->rx_block_stride, wce::NSC))
-        return fail(WCE_EINVAL, "wce_combine: rx strides too small");
-    if (p->h_stride < wce::NSC) return fail(WCE_EINVAL, "wce_combine: h_stride < 53");
-    if (out->rx && !strides_hold(n, out->rx_frame_stride, out->rx_block_stride, wce::NSC))
-        return fail(WCE_EINVAL, "wce_combine: output rx strides too small");
-    if (out->h && out->h_stride < wce::NSC) return fail(WCE_EINVAL, "wce_combine: output h_stride < 53");
-    if (!branches_apart(A, p->rx_branch_stride, n, p->rx_frame_stride, p->rx_block_stride))
-        return fail(WCE_EINVAL, "wce_combine: rx_branch_stride makes branches overlap");
-    if (!rows_apart(A, p->h_branch_stride, n, p->h_stride))
-        return fail(WCE_EINVAL, "wce_combine: h_branch_stride makes branches overlap");
-    if (p->ow2 && A > 1 && p->ow2_branch_stride < n)
-        return fail(WCE_EINVAL, "wce_combine: ow2_branch_stride < n_frames");
-    if (reinterpret_cast<uintptr_t>(p->rx) % 16 || reinterpret_cast<uintptr_t>(p->h) % 16 ||
-        reinterpret_cast<uintptr_t>(out->rx) % 16 || reinterpret_cast<uintptr_t>(out->h) % 16)
-        return fail(WCE_EINVAL, "wce_combine: rx, h or an output not 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(p->ow2) % 8) return fail(WCE_EINVAL, "wce_combine: ow2 not 8-byte aligned");
-    if (n == 0) return WCE_OK;
-    wce::CombineArgs a{};
-    a.rx = reinterpret_cast<const double *>(p->rx);
-    a.h = reinterpret_cast<const double *>(p->h);
-    a.ow2 = p->ow2;
-    a.rbs = A > 1 ? p->rx_branch_stride : 0; a.rfs = p->rx_frame_stride; a.rks = p->rx_block_stride;
-    a.hbs = A > 1 ? p->h_branch_stride : 0; a.hs = p->h_stride;
-    a.obs = A > 1 ? p->ow2_branch_stride : 0; a.n = n; a.na = (int32_t)A;
-    a.orx = reinterpret_cast<double *>(out->rx);
-    a.ofs = out->rx_frame_stride; a.oks = out->rx_block_stride;
-    a.oh = reinterpret_cast<double *>(out->h);
-    a.ohs = out->h_stride;
-    DeviceGuard g(c->device);
-    const int rc = wce::launch_combine(a, stream);
-    return rc ? fail(rc, "combine launch") : WCE_OK;
-}
-
-int wce_sync_share(wce_ctx *c, int32_t n_branches, int64_t branch_stride, int64_t n_packets, const double *metric,
-                   int32_t *start, double *cfo, void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (!metric || reinterpret_cast<uintptr_t>(metric) % 8)
-        return fail(WCE_EINVAL, "wce_sync_share: metric null or not 8-byte aligned");
-    if (!start && !cfo) return fail(WCE_EINVAL, "wce_sync_share: start and cfo both null");
-    if (reinterpret_cast<uintptr_t>(start) % 4) return fail(WCE_EINVAL, "wce_sync_share: start not 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(cfo) % 8) return fail(WCE_EINVAL, "wce_sync_share: cfo not 8-byte aligned");
-    if (n_branches < 1 || n_branches > WCE_COMBINE_MAX_BRANCHES)
-        return fail(WCE_EINVAL, "wce_sync_share: n_branches outside 1..8");
-    if (n_packets < 0 || n_packets > 0x7fffffffll)
-        return fail(WCE_EINVAL, "wce_sync_share: n_packets < 0 or > 2^31 - 1");
-    if (n_branches > 1 && branch_stride < n_packets)
-        return fail(WCE_EINVAL, "wce_sync_share: branch_stride < n_packets");
-    if (n_packets == 0) return WCE_OK;
-    wce::SyncShareArgs a{};
-    a.metric = metric; a.start = start; a.cfo = cfo;
-    a.bs = n_branches > 1 ? branch_stride : 0; a.n = n_packets; a.na = n_branches;
-    DeviceGuard g(c->device);
-    const int rc = wce::launch_sync_share(a, stream);
-    return rc ? fail(rc, "sync_share launch") : WCE_OK;
-}
-
-// ---------------------------------------------------------------- decoding
-int wce_decode_info_bits(int32_t modulation, int32_t rate)
-{
-    const int T = wce::decode_info_bits(modulation, rate);
-    return T < 0 ? fail(WCE_EINVAL, "wce_decode_info_bits: unknown modulation or rate") : T;
-}
-
-// block stride >= row and, with more than one frame, frame stride >= 14 block strides + one row
-static bool strides_hold(int64_t n, int64_t fs, int64_t bs, int64_t row)
-{
-    return bs >= row && (n <= 1 || fs >= (wce::NBLK - 1) * bs + row);
-}
-
-int wce_soft_demap(wce_ctx *c, const wce_complex *eq, int64_t eq_frame_stride, int64_t eq_block_stride,
-                   const wce_demod *p, int64_t n, float *llr, int64_t llr_frame_stride, int64_t llr_block_stride,
-                   void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (!eq || !p || !llr) return fail(WCE_EINVAL, "wce_soft_demap: null eq, parameters or llr");
-    if (!p->h) return fail(WCE_EINVAL, "wce_soft_demap: h required");
-    if (p->h_stride < wce::NSC) return fail(WCE_EINVAL, "wce_soft_demap: h_stride < 53");
-    double K;
-    switch (p->modulation) {   // the doubles nearest to 1 / sqrt(1, 2, 10, 42), as wce_demodulate
-    case WCE_MOD_BPSK: K = 1.0; break;
-    case WCE_MOD_QPSK: K = 0.70710678118654752440; break;
-    case WCE_MOD_QAM16: K = 0.31622776601683793320; break;
-    case WCE_MOD_QAM64: K = 0.15430334996209191026; break;
-    default: return fail(WCE_EINVAL, "wce_soft_demap: unknown modulation");
-    }
-    if (!(p->scale > 0.0) || p->scale * 0.0 != 0.0) return fail(WCE_EINVAL, "wce_soft_demap: scale not positive and finite");
-    if (n < 0 || n > 0x7fffffffll) return fail(WCE_EINVAL, "wce_soft_demap: n_frames < 0 or > 2^31 - 1");
-    if (!strides_hold(n, eq_frame_stride, eq_block_stride, wce::NSC))
-        return fail(WCE_EINVAL, "wce_soft_demap: eq strides too small");
-    if (!strides_hold(n, llr_frame_stride, llr_block_stride, 48 * (int64_t)p->modulation))
-        return fail(WCE_EINVAL, "wce_soft_demap: llr strides too small");
-    if (reinterpret_cast<uintptr_t>(eq) % 16 || reinterpret_cast<uintptr_t>(p->h) % 16 ||
-        reinterpret_cast<uintptr_t>(p->h_lt) % 16)
-        return fail(WCE_EINVAL, "wce_soft_demap: eq, h or h_lt not 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(llr) % 4) return fail(WCE_EINVAL, "wce_soft_demap: llr not 4-byte aligned");
-    if (n == 0) return WCE_OK;
-    wce::DemapArgs a{};
-    a.eq = reinterpret_cast<const double *>(eq);
-    a.h = reinterpret_cast<const double *>(p->h);
-    a.hlt = reinterpret_cast<const double *>(p->h_lt);
-    a.efs = eq_frame_stride; a.ebs = eq_block_stride; a.hs = p->h_stride; a.n = n;
-    a.mod = p->modulation; a.d = p->scale * K;
-    a.llr = llr; a.lfs = llr_frame_stride; a.lbs = llr_block_stride;
-    DeviceGuard g(c->device);
-    const int rc = wce::launch_demap(a, stream);
-    return rc ? fail(rc, "soft demap launch") : WCE_OK;
-}
-
-int wce_soft_demap_blocks(wce_ctx *c, const wce_complex *eq, int64_t eq_frame_stride, int64_t eq_block_stride,
-                          const wce_complex *hb, int64_t hb_frame_stride, int64_t hb_block_stride, int32_t modulation,
-                          double scale, int64_t n, float *llr, int64_t llr_frame_stride, int64_t llr_block_stride,
-                          void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (!eq || !hb || !llr) return fail(WCE_EINVAL, "wce_soft_demap_blocks: null eq, hb or llr");
-    const double K = mod_K(modulation);
-    if (K == 0.0) return fail(WCE_EINVAL, "wce_soft_demap_blocks: unknown modulation");
-    if (!(scale > 0.0) || scale * 0.0 != 0.0)
-        return fail(WCE_EINVAL, "wce_soft_demap_blocks: scale not positive and finite");
-    if (n < 0 || n > 0x7fffffffll) return fail(WCE_EINVAL, "wce_soft_demap_blocks: n_frames < 0 or > 2^31 - 1");
-    if (!strides_hold(n, eq_frame_stride, eq_block_stride, wce::NSC))
-        return fail(WCE_EINVAL, "wce_soft_demap_blocks: eq strides too small");
-    if (!strides_hold(n, hb_frame_stride, hb_block_stride, wce::NSC))
-        return fail(WCE_EINVAL, "wce_soft_demap_blocks: hb strides too small");
-    if (!strides_hold(n, llr_frame_stride, llr_block_stride, 48 * (int64_t)modulation))
-        return fail(WCE_EINVAL, "wce_soft_demap_blocks: llr strides too small");
-    if (reinterpret_cast<uintptr_t>(eq) % 16 || reinterpret_cast<uintptr_t>(hb) % 16)
-        return fail(WCE_EINVAL, "wce_soft_demap_blocks: eq or hb not 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(llr) % 4) return fail(WCE_EINVAL, "wce_soft_demap_blocks: llr not 4-byte aligned");
-    if (n == 0) return WCE_OK;
-    wce::DemapArgs a{};
-    a.eq = reinterpret_cast<const double *>(eq);
-    a.hb = reinterpret_cast<const double *>(hb);
-    a.hbfs = hb_frame_stride; a.hbbs = hb_block_stride;
-    a.efs = eq_frame_stride; a.ebs = eq_block_stride; a.n = n;
-    a.mod = modulation; a.d = scale * K;
-    a.llr = llr; a.lfs = llr_frame_stride; a.lbs = llr_block_stride;
-    DeviceGuard g(c->device);
-    const int rc = wce::launch_demap(a, stream);
-    return rc ? fail(rc, "soft demap launch") : WCE_OK;
-}
-
-int wce_viterbi_decode(wce_ctx *c, const float *llr, int64_t llr_frame_stride, int64_t llr_block_stride,
-                       int32_t modulation, int32_t rate, uint32_t flags, int64_t n, uint8_t *bits,
-                       int64_t bits_stride, const uint8_t *ref_bits, int64_t ref_stride, uint32_t *nbiterr,
-                       void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (!llr) return fail(WCE_EINVAL, "wce_viterbi_decode: null llr");
-    const int T = wce::decode_info_bits(modulation, rate);
-    if (T < 0) return fail(WCE_EINVAL, "wce_viterbi_decode: unknown modulation or rate");
-    if (flags & ~WCE_DEC_TERMINATED) return fail(WCE_EINVAL, "wce_viterbi_decode: unknown flag bits");
-    if (!bits && !nbiterr) return fail(WCE_EINVAL, "wce_viterbi_decode: no output requested");
-    if (nbiterr && !ref_bits) return fail(WCE_EINVAL, "wce_viterbi_decode: nbiterr needs ref_bits");
-    if (n < 0 || n > 0x7fffffffll) return fail(WCE_EINVAL, "wce_viterbi_decode: n_frames < 0 or > 2^31 - 1");
-    if (!strides_hold(n, llr_frame_stride, llr_block_stride, 48 * (int64_t)modulation))
-        return fail(WCE_EINVAL, "wce_viterbi_decode: llr strides too small");
-    const int64_t nbytes = (T + 7) / 8;
-    if (bits && bits_stride < nbytes) return fail(WCE_EINVAL, "wce_viterbi_decode: bits_stride < ceil(T / 8)");
-    if (ref_bits && ref_stride < nbytes) return fail(WCE_EINVAL, "wce_viterbi_decode: ref_stride < ceil(T / 8)");
-    if (reinterpret_cast<uintptr_t>(llr) % 4 || reinterpret_cast<uintptr_t>(nbiterr) % 4)
-        return fail(WCE_EINVAL, "wce_viterbi_decode: llr or nbiterr not 4-byte aligned");
-    if (n == 0) return WCE_OK;
-    wce::ViterbiArgs a{};
-    a.llr = llr; a.lfs = llr_frame_stride; a.lbs = llr_block_stride; a.n = n;
-    a.mod = modulation; a.rate = rate; a.T = T; a.flags = flags;
-    a.bits = bits; a.bits_stride = bits_stride;
-    a.ref = ref_bits; a.ref_stride = ref_stride;
-    a.nbiterr = nbiterr;
-    DeviceGuard g(c->device);
-    const int rc = wce::launch_viterbi(a, stream);
-    if (rc == WCE_EINVAL) return fail(rc, "wce_viterbi_decode: the survivor memory of T steps does not fit the LDS");
-    return rc ? fail(rc, "viterbi launch") : WCE_OK;
-}
-
-// ---------------------------------------------------------------- decision-directed estimation
-int wce_reencode(wce_ctx *c, const wce_reencode_par *p, const wce_frames *in, int64_t n,
-                 const wce_reencode_out *out, void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (!p || !out) return fail(WCE_EINVAL, "wce_reencode: null parameters or outputs");
-    if (!p->bits) return fail(WCE_EINVAL, "wce_reencode: bits required");
-    if (!out->tx && !out->h) return fail(WCE_EINVAL, "wce_reencode: no output requested");
-    if (out->h && (!in || !in->rx)) return fail(WCE_EINVAL, "wce_reencode: h needs the frames' rx");
-    if (n < 0 || n > 0x7fffffffll) return fail(WCE_EINVAL, "wce_reencode: n_frames < 0 or > 2^31 - 1");
-    if (in && in->n_frames != n) return fail(WCE_EINVAL, "wce_reencode: the frames' n_frames differs from n_frames");
-    const int T = wce::decode_info_bits(p->modulation, p->rate);
-    if (T < 0) return fail(WCE_EINVAL, "wce_reencode: unknown modulation or rate");
-    double K;
-    switch (p->modulation) {   // the doubles nearest to 1 / sqrt(1, 2, 10, 42), as wce_demodulate
-    case WCE_MOD_BPSK: K = 1.0; break;
-    case WCE_MOD_QPSK: K = 0.70710678118654752440; break;
-    case WCE_MOD_QAM16: K = 0.31622776601683793320; break;
-    default: K = 0.15430334996209191026; break;
-    }
-    if (!(p->scale > 0.0) || p->scale * 0.0 != 0.0) return fail(WCE_EINVAL, "wce_reencode: scale not positive and finite");
-    if (p->bits_stride < (T + 7) / 8) return fail(WCE_EINVAL, "wce_reencode: bits_stride < ceil(T / 8)");
-    if (out->tx && !strides_hold(n, out->tx_frame_stride, out->tx_block_stride, wce::NSC))
-        return fail(WCE_EINVAL, "wce_reencode: tx strides too small");
-    if (in && !strides_hold(n, in->frame_stride, in->block_stride, wce::NSC))
-        return fail(WCE_EINVAL, "wce_reencode: the frames' strides too small");
-    if (out->h && out->h_stride < wce::NSC) return fail(WCE_EINVAL, "wce_reencode: h_stride < 53");
-    if (reinterpret_cast<uintptr_t>(out->tx) % 16 || reinterpret_cast<uintptr_t>(out->h) % 16 ||
-        (in && (reinterpret_cast<uintptr_t>(in->rx) % 16 || reinterpret_cast<uintptr_t>(in->tx) % 16)))
-        return fail(WCE_EINVAL, "wce_reencode: tx, h or the frames' rx or tx not 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(p->theta) % 8) return fail(WCE_EINVAL, "wce_reencode: theta not 8-byte aligned");
-    if (n == 0) return WCE_OK;
-    wce::ReencodeArgs a{};
-    a.bits = p->bits; a.bits_stride = p->bits_stride;
-    a.theta = out->h ? p->theta : nullptr;
-    a.ptx = in ? reinterpret_cast<const double *>(in->tx) : nullptr;
-    a.rx = out->h ? reinterpret_cast<const double *>(in->rx) : nullptr;
-    if (in) { a.fs = in->frame_stride; a.bs = in->block_stride; }
-    a.n = n; a.mod = p->modulation; a.rate = p->rate;
-    a.scale = p->scale; a.d = p->scale * K;
-    a.tx = reinterpret_cast<double *>(out->tx); a.tfs = out->tx_frame_stride; a.tbs = out->tx_block_stride;
-    a.h = reinterpret_cast<double *>(out->h); a.hs = out->h_stride;
-    DeviceGuard g(c->device);
-    const int rc = wce::launch_reencode(a, stream);
-    return rc ? fail(rc, "reencode launch") : WCE_OK;
-}
-
-// ---------------------------------------------------------------- framing the payload
-int wce_psdu_max_len(int32_t modulation, int32_t rate)
-{
-    const int T = wce::decode_info_bits(modulation, rate);
-    return T < 0 ? fail(WCE_EINVAL, "wce_psdu_max_len: unknown modulation or rate") : (T - 22) / 8;
-}
-
-// what both calls ask of p, n_frames and bits_stride; null when it holds, else what is wrong.  Fills T, nbytes,
-// max_len, length, seed, lengths, seeds, bits_stride and n of `a`
-static const char *check_psdu(const wce_psdu_par *p, int64_t n, int64_t bits_stride, bool framing, wce::PsduArgs *a)
-{
-    const int T = wce::decode_info_bits(p->modulation, p->rate);
-    if (T < 0) return "unknown modulation or rate";
-    const int32_t max = (T - 22) / 8;
-    if (!p->lengths && (p->length < 4 || p->length > max)) return "length outside 4..max";
-    if (framing && !p->seeds && (p->seed < 1 || p->seed > 127)) return "seed outside 1..127";
-    if (bits_stride < (T + 7) / 8) return "bits_stride < ceil(T / 8)";
-    if (reinterpret_cast<uintptr_t>(p->lengths) % 4) return "lengths not 4-byte aligned";
-    if (n < 0 || n > 0x7fffffffll) return "n_frames < 0 or > 2^31 - 1";
-    a->T = T; a->nbytes = (T + 7) / 8; a->max_len = max;
-    a->length = p->lengths ? max : p->length;
-    a->seed = framing && !p->seeds ? p->seed : 1;
-    a->lengths = p->lengths;
-    a->seeds = framing ? p->seeds : nullptr;
-    a->bits_stride = bits_stride; a->n = n;
-    return nullptr;
-}
-
-int wce_psdu_frame(wce_ctx *c, const wce_psdu_par *p, const uint8_t *payload, int64_t payload_stride, int64_t n,
-                   uint8_t *bits, int64_t bits_stride, void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (!p || !bits) return fail(WCE_EINVAL, "wce_psdu_frame: null parameters or bits");
-    wce::PsduArgs a{};
-    if (const char *what = check_psdu(p, n, bits_stride, true, &a))
-        return fail(WCE_EINVAL, (std::string("wce_psdu_frame: ") + what).c_str());
-    if (!payload && (p->lengths || p->length > 4))
-        return fail(WCE_EINVAL, "wce_psdu_frame: payload NULL with length > 4 or with lengths");
-    if (payload && payload_stride < a.length - 4)
-        return fail(WCE_EINVAL, "wce_psdu_frame: payload_stride < L - 4 (max - 4 with lengths)");
-    if (n == 0) return WCE_OK;
-    a.payload = payload; a.payload_stride = payload ? payload_stride : 0;
-    a.bits_w = bits;
-    DeviceGuard g(c->device);
-    const int rc = wce::launch_psdu_frame(a, stream);
-    return rc ? fail(rc, "psdu frame launch") : WCE_OK;
-}
-
-int wce_psdu_deframe(wce_ctx *c, const wce_psdu_par *p, const uint8_t *bits, int64_t bits_stride, int64_t n,
-                     const wce_psdu_out *out, void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (!p || !bits || !out) return fail(WCE_EINVAL, "wce_psdu_deframe: null parameters, bits or outputs");
-    if (!out->psdu && !out->seed && !out->fcs_ok && !out->n_good)
-        return fail(WCE_EINVAL, "wce_psdu_deframe: no output requested");
-    wce::PsduArgs a{};
-    if (const char *what = check_psdu(p, n, bits_stride, false, &a))
-        return fail(WCE_EINVAL, (std::string("wce_psdu_deframe: ") + what).c_str());
-    if (out->psdu && out->psdu_stride < a.length)
-        return fail(WCE_EINVAL, "wce_psdu_deframe: psdu_stride < L (max with lengths)");
-    if (reinterpret_cast<uintptr_t>(out->fcs_ok) % 4 || reinterpret_cast<uintptr_t>(out->n_good) % 4)
-        return fail(WCE_EINVAL, "wce_psdu_deframe: fcs_ok or n_good not 4-byte aligned");
-    if (n == 0) return WCE_OK;
-    a.bits_r = bits;
-    a.psdu = out->psdu; a.psdu_stride = out->psdu_stride;
-    a.oseed = out->seed; a.fcs_ok = out->fcs_ok; a.n_good = out->n_good;
-    DeviceGuard g(c->device);
-    const int rc = wce::launch_psdu_deframe(a, stream);
-    return rc ? fail(rc, "psdu deframe launch") : WCE_OK;
-}
-
-// ---------------------------------------------------------------- transmitter and channel
-static bool misaligned(const void *p, uintptr_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
-
-// the symbol side of wce_modulate and wce_transmit; null when it holds, else what is wrong
-static const char *check_symbols(const wce_complex *tx_pre, int64_t pre_stride, const wce_complex *sym,
-                                 int64_t frame_stride, int64_t block_stride, int32_t n_blocks, int64_t n_frames)
-{
-    if (n_blocks < 0 || n_blocks > wce::NBLK) return "n_blocks outside 0..15";
-    if (!tx_pre && n_blocks == 0) return "no field and n_blocks == 0";
-    if (n_blocks > 0 && !sym) return "sym required";
-    if (n_frames < 0 || n_frames > 0x7fffffffll) return "n_frames < 0 or > 2^31 - 1";
-    if (n_blocks > 0 && block_stride < wce::NSC) return "block_stride < 53";
-    if (n_blocks > 0 && n_frames > 1 && frame_stride < (int64_t)(n_blocks - 1) * block_stride + wce::NSC)
-        return "frame_stride < (n_blocks - 1) block_stride + 53";
-    if (tx_pre && pre_stride != 0 && pre_stride < wce::NSC) return "pre_stride neither 0 nor >= 53";
-    if (misaligned(tx_pre, 16) || misaligned(sym, 16)) return "tx_pre or sym not 16-byte aligned";
-    return nullptr;
-}
-
-// p and the capture side of wce_channel and wce_transmit
-static const char *check_channel(const wce_channel_par *p, const wce_complex *capture, int64_t capture_stride,
-                                 int64_t capture_len, int64_t n_frames)
-{
-    if (!p || !capture) return "null parameters or capture";
-    if (n_frames < 0 || n_frames > 0x7fffffffll) return "n_frames < 0 or > 2^31 - 1";
-    if (p->n_taps < 1 || p->n_taps > 16) return "n_taps outside 1..16";
-    if (p->taps && p->taps_stride != 0 && p->taps_stride < p->n_taps) return "taps_stride neither 0 nor >= n_taps";
-    if (capture_len < 1 || capture_len > 0x7fffffffll) return "capture_len < 1 or >= 2^31";
-    if (capture_stride < capture_len) return "capture_stride < capture_len";
-    if (misaligned(p->taps, 16) || misaligned(capture, 16)) return "taps or capture not 16-byte aligned";
-    if (misaligned(p->cfo, 8) || misaligned(p->ow2, 8)) return "cfo or ow2 not 8-byte aligned";
-    if (misaligned(p->delay, 4)) return "delay not 4-byte aligned";
-    return nullptr;
-}
-
-static void tx_symbols(wce::TxArgs &a, const wce_complex *tx_pre, int64_t pre_stride, const wce_complex *sym,
-                       int64_t frame_stride, int64_t block_stride, int32_t n_blocks)
-{
-    a.pre = reinterpret_cast<const double *>(tx_pre); a.pre_stride = pre_stride;
-    a.sym = reinterpret_cast<const double *>(sym); a.fs = frame_stride; a.bs = block_stride;
-    a.nb = n_blocks; a.field = tx_pre ? 1 : 0;
-}
-
-static void tx_channel(wce::TxArgs &a, const wce_channel_par *p, int field, wce_complex *capture,
-                       int64_t capture_stride, int64_t capture_len)
-{
-    a.taps = reinterpret_cast<const double *>(p->taps); a.ts = p->taps_stride;
-    a.nt = p->taps ? p->n_taps : 1;
-    a.chan_field = field;
-    a.cfo = p->cfo; a.ow2 = p->ow2; a.delay = p->delay; a.seed = p->seed; a.first = p->first_frame;
-    a.out = reinterpret_cast<double *>(capture); a.os = capture_stride; a.olen = capture_len;
-}
-
-int wce_modulate(wce_ctx *c, const wce_complex *tx_pre, int64_t pre_stride, const wce_complex *sym,
-                 int64_t frame_stride, int64_t block_stride, int32_t n_blocks, int64_t n_frames, wce_complex *wave,
-                 int64_t wave_stride, void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (!wave) return fail(WCE_EINVAL, "wce_modulate: wave required");
-    const char *bad = check_symbols(tx_pre, pre_stride, sym, frame_stride, block_stride, n_blocks, n_frames);
-    if (bad) return fail(WCE_EINVAL, (std::string("wce_modulate: ") + bad).c_str());
-    if (wave_stride < (tx_pre ? 160 : 0) + 80 * (int64_t)n_blocks)
-        return fail(WCE_EINVAL, "wce_modulate: wave_stride < the waveform's length");
-    if (misaligned(wave, 16)) return fail(WCE_EINVAL, "wce_modulate: wave not 16-byte aligned");
-    if (n_frames == 0) return WCE_OK;
-    wce::TxArgs a{};
-    tx_symbols(a, tx_pre, pre_stride, sym, frame_stride, block_stride, n_blocks);
-    a.out = reinterpret_cast<double *>(wave); a.os = wave_stride; a.n = n_frames;
-    DeviceGuard g(c->device);
-    const int rc = wce::launch_modulate(a, stream);
-    return rc ? fail(rc, "modulate launch") : WCE_OK;
-}
-
-int wce_channel(wce_ctx *c, const wce_complex *wave, int64_t wave_stride, int64_t wave_len, int64_t n_frames,
-                const wce_channel_par *p, wce_complex *capture, int64_t capture_stride, int64_t capture_len,
-                void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (!wave) return fail(WCE_EINVAL, "wce_channel: wave required");
-    const char *bad = check_channel(p, capture, capture_stride, capture_len, n_frames);
-    if (bad) return fail(WCE_EINVAL, (std::string("wce_channel: ") + bad).c_str());
-    if (wave_len < 1 || wave_len > 0x7fffffffll) return fail(WCE_EINVAL, "wce_channel: wave_len < 1 or >= 2^31");
-    if (wave_stride < wave_len) return fail(WCE_EINVAL, "wce_channel: wave_stride < wave_len");
-    if (misaligned(wave, 16)) return fail(WCE_EINVAL, "wce_channel: wave not 16-byte aligned");
-    if (n_frames == 0) return WCE_OK;
-    wce::TxArgs a{};
-    a.wave = reinterpret_cast<const double *>(wave); a.ws = wave_stride; a.wlen = wave_len; a.n = n_frames;
-    tx_channel(a, p, p->field ? 1 : 0, capture, capture_stride, capture_len);
-    DeviceGuard g(c->device);
-    const int rc = wce::launch_channel(a, stream);
-    return rc ? fail(rc, "channel launch") : WCE_OK;
-}
-
-int wce_transmit(wce_ctx *c, const wce_complex *tx_pre, int64_t pre_stride, const wce_complex *sym,
-                 int64_t frame_stride, int64_t block_stride, int32_t n_blocks, int64_t n_frames,
-                 const wce_channel_par *p, wce_complex *capture, int64_t capture_stride, int64_t capture_len,
-                 void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    const char *bad = check_symbols(tx_pre, pre_stride, sym, frame_stride, block_stride, n_blocks, n_frames);
-    if (!bad) bad = check_channel(p, capture, capture_stride, capture_len, n_frames);
-    if (bad) return fail(WCE_EINVAL, (std::string("wce_transmit: ") + bad).c_str());
-    if (n_frames == 0) return WCE_OK;
-    wce::TxArgs a{};
-    tx_symbols(a, tx_pre, pre_stride, sym, frame_stride, block_stride, n_blocks);
-    a.n = n_frames;
-    tx_channel(a, p, a.field, capture, capture_stride, capture_len);
-    DeviceGuard g(c->device);
-    const int rc = wce::launch_transmit(a, stream);
-    return rc ? fail(rc, "transmit launch") : WCE_OK;
-}
-
-// ---- the time-varying pair: the static calls' checks on the fields the two structures share, then the knots'
-static wce_channel_par static_side(const wce_fading_par *p)
-{
-    return wce_channel_par{nullptr, 0, p->n_taps, p->field, p->cfo, p->ow2, p->delay, p->seed, p->first_frame};
-}
-
-static const char *check_fading(const wce_fading_par *p, wce_complex *capture, int64_t capture_stride,
-                                int64_t capture_len, int64_t n_frames)
-{
-    if (!p) return "null parameters or capture";
-    const wce_channel_par s = static_side(p);
-    if (const char *bad = check_channel(&s, capture, capture_stride, capture_len, n_frames)) return bad;
-    if (!p->knots) return "knots required";
-    if (misaligned(p->knots, 16)) return "knots not 16-byte aligned";
-    if (p->n_knots < 2) return "n_knots < 2";
-    if (p->knot_period < 16 || p->knot_period > (1 << 20)) return "knot_period outside 16..2^20";
-    if (p->knot_stride < p->n_taps) return "knot_stride < n_taps";
-    if (p->frame_stride != 0 && p->frame_stride < (int64_t)(p->n_knots - 1) * p->knot_stride + p->n_taps)
-        return "frame_stride neither 0 nor >= (n_knots - 1) knot_stride + n_taps";
-    return nullptr;
-}
-
-// the knots reach past the last output of a waveform of wave_len samples
-static bool knots_cover(const wce_fading_par *p, int64_t wave_len)
-{
-    return (int64_t)(p->n_knots - 1) * p->knot_period > wave_len + p->n_taps - 2;
-}
-
-static void tx_knots(wce::TxTvArgs &g, const wce_fading_par *p)
-{
-    g.k.knots = reinterpret_cast<const double *>(p->knots); g.k.fs = p->frame_stride; g.k.ks = p->knot_stride;
-    g.k.nk = p->n_knots; g.k.period = p->knot_period;
-}
-
-int wce_channel_tv(wce_ctx *c, const wce_complex *wave, int64_t wave_stride, int64_t wave_len, int64_t n_frames,
-                   const wce_fading_par *p, wce_complex *capture, int64_t capture_stride, int64_t capture_len,
-                   void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    if (!wave) return fail(WCE_EINVAL, "wce_channel_tv: wave required");
-    const char *bad = check_fading(p, capture, capture_stride, capture_len, n_frames);
-    if (bad) return fail(WCE_EINVAL, (std::string("wce_channel_tv: ") + bad).c_str());
-    if (wave_len < 1 || wave_len > 0x7fffffffll) return fail(WCE_EINVAL, "wce_channel_tv: wave_len < 1 or >= 2^31");
-    if (wave_stride < wave_len) return fail(WCE_EINVAL, "wce_channel_tv: wave_stride < wave_len");
-    if (misaligned(wave, 16)) return fail(WCE_EINVAL, "wce_channel_tv: wave not 16-byte aligned");
-    if (!knots_cover(p, wave_len)) return fail(WCE_EINVAL, "wce_channel_tv: the knots do not cover the output");
-    if (n_frames == 0) return WCE_OK;
-    wce::TxTvArgs g{};
-    g.a.wave = reinterpret_cast<const double *>(wave); g.a.ws = wave_stride; g.a.wlen = wave_len; g.a.n = n_frames;
-    const wce_channel_par s = static_side(p);
-    tx_channel(g.a, &s, p->field ? 1 : 0, capture, capture_stride, capture_len);
-    g.a.nt = p->n_taps;
-    tx_knots(g, p);
-    DeviceGuard dg(c->device);
-    const int rc = wce::launch_channel_tv(g, stream);
-    return rc ? fail(rc, "channel_tv launch") : WCE_OK;
-}
-
-int wce_transmit_tv(wce_ctx *c, const wce_complex *tx_pre, int64_t pre_stride, const wce_complex *sym,
-                    int64_t frame_stride, int64_t block_stride, int32_t n_blocks, int64_t n_frames,
-                    const wce_fading_par *p, wce_complex *capture, int64_t capture_stride, int64_t capture_len,
-                    void *stream)
-{
-    if (!c) return fail(WCE_EINVAL, "null ctx");
-    const char *bad = check_symbols(tx_pre, pre_stride, sym, frame_stride, block_stride, n_blocks, n_frames);
-    if (!bad) bad = check_fading(p, capture, capture_stride, capture_len, n_frames);
-    if (bad) return fail(WCE_EINVAL, (std::string("wce_transmit_tv: ") + bad).c_str());
-    if (!knots_cover(p, (tx_pre ? 160 : 0) + 80 * (int64_t)n_blocks))
-        return fail(WCE_EINVAL, "wce_transmit_tv: the knots do not cover the output");
-    if (n_frames == 0) return WCE_OK;
-    wce::TxTvArgs g{};
-    tx_symbols(g.a, tx_pre, pre_stride, sym, frame_stride, block_stride, n_blocks);
-    g.a.n = n_frames;
-    const wce_channel_par s = static_side(p);
-    tx_channel(g.a, &s, g.a.field, capture, capture_stride, capture_len);
-    g.a.nt = p->n_taps;
-    tx_knots(g, p);
-    DeviceGuard dg(c->device);
-    const int rc = wce::launch_transmit_tv(g, stream);
-    return rc ? fail(rc, "transmit_tv launch") : WCE_OK;
-}
-
 // ---------------------------------------------------------------- runtime helpers
 int wce_device_count(int *count)
 {
@@ -1818,56 +926,21 @@ extern "C" int wce_debug_set_variant(int which, int value)
     return rc ? fail(rc, "variant: which in [0, 7), value in [0, 32)") : WCE_OK;
 }
 
-extern "C" long long wce_debug_chain_grid(long long blocks, long long own_cap)
-{
-    return wce::chain_grid(blocks, own_cap);
-}
-
-extern "C" int wce_debug_short_field_period(double *out)
-{
-    if (!out) return fail(WCE_EINVAL, "null buffer");
-    wce::short_field_period(out);
-    return WCE_OK;
-}
-
-extern "C" int wce_debug_sync_stf_tiles(int *lags_stf, int *lags_ltf)
-{
-    if (!lags_stf || !lags_ltf) return fail(WCE_EINVAL, "null buffer");
-    wce::sync_stf_tiles(lags_stf, lags_ltf);
-    return WCE_OK;
-}
-
 extern "C" int wce_debug_set_flat_chunk(long long frames)
 {
     const int rc = wce::set_flat_chunk(frames);
     return rc ? fail(rc, "flat chunk: 0, or a multiple of 32 in [32, 2^26]") : WCE_OK;
 }
 
-// ---- internal hooks for wce_multi.cpp (wce_internal.h)
+// ---- internal hooks for wce_multi.cpp (wce_internal.h) and wce_chain_api.cpp (wce_api_check.h)
 namespace wce {
-int api_fail(int code, const char *what) { return fail(code, what); }
-int ctx_device(const wce_ctx *c) { return c ? c->device : -1; }
-bool ctx_ready(const wce_ctx *c) { return c && c->ready; }
-
-// 802.11a's short sequence on the bins k = -24, -20 .. 24 without DC: the signs of sqrt(13/6) (1 + j)
-static const int kShortSign[12] = {+1, -1, +1, -1, -1, +1, -1, -1, +1, +1, +1, +1};
-
-void short_field_period(double *t32)
+int api_fail(int code, const char *what)
 {
-    const long double pi = 3.14159265358979323846264338327950288L;
-    const long double amp = sqrtl(13.0L / 6.0L) / 64.0L;
-    for (int m = 0; m < 16; ++m) {
-        // t[m] = (1/64) sum_k S_k exp(2 pi i k m / 64), k = 4 j: the twiddle's argument is (j m mod 16) / 16 of a turn
-        long double re = 0.0L, im = 0.0L;
-        for (int i = 0; i < 12; ++i) {
-            const int j = i < 6 ? i - 6 : i - 5;
-            const int turn = ((j * m) % 16 + 16) % 16;
-            const long double cs = cosl(2.0L * pi * turn / 16.0L), sn = sinl(2.0L * pi * turn / 16.0L);
-            re += kShortSign[i] * (cs - sn);   // (1 + j) (cs + j sn)
-            im += kShortSign[i] * (cs + sn);
-        }
-        t32[2 * m] = (double)(amp * re);
-        t32[2 * m + 1] = (double)(amp * im);
-    }
+    g_err = what;
+    return code;
 }
+int ctx_device(const wce_ctx *c) { return c ? c->device : -1; }
+int ctx_cus(const wce_ctx *c) { return c->cus; }
+bool ctx_ready(const wce_ctx *c) { return c && c->ready; }
+int api_check_frames(const wce_frames *in, bool need_blocks) { return check_frames(in, need_blocks); }
 }  // namespace wce
