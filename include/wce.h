@@ -168,6 +168,24 @@ typedef struct {
     int32_t semantics;          /* WCE_SEM_C (main.c) or WCE_SEM_MATLAB (WiFi_*.m) */
 } wce_frames;
 
+/* Frames: what a frame's outputs may depend on.  In every call that takes a batch
+ * (wce_frames, n_frames, n_packets) the outputs of frame f depend on frame f's
+ * own inputs and on the arguments every frame shares (the context, strides, masks,
+ * scalars, shared arrays such as tx_pre or ltf), and on nothing else: not on f,
+ * not on the batch size, not on what any other frame holds, non-finite values
+ * included.  So a batch permuted gives the same rows permuted, a slice of a batch
+ * run alone gives the slice of the rows, and both hold bit for bit.
+ *  - Indexed calls add one thing: wce_synth_frames, wce_channel, wce_transmit and
+ *    their _tv forms key their random numbers on the global index first_frame + f.
+ *    A slice [s, s + n) run with first_frame raised by s gives the slice of the
+ *    rows; with the noise off (ow2 = 0 or NULL) they are as every other call.
+ *  - Totals are sums: a batch-wide count (wce_psdu_deframe's *n_good increment,
+ *    wce_nonfinite_scan's *n_bad) is the sum of its per-frame flags.
+ *  - wce_combine and wce_sync_share are branch-major: the law holds per packet,
+ *    across all of its branches.
+ * tests/frame_model.py is the table of the calls, and tests/test_frame_law_gpu.py
+ * holds each to it. */
+
 /* Estimator semantics (wce_frames.semantics):
  *  WCE_SEM_C      : main.c -- one OFDM block (`block`), LT_LS "conj" quirk
  *                   (main.c:69), every cubic divided difference by 14 (main.c:116-118).

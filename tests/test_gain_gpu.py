@@ -223,19 +223,30 @@ def _estimate_set(B):
                 x_ref=np.array(g["tx_symb"][0], np.complex128))
 
 
+VARIANT_DEFAULT = {1: 2}             # wce_debug_set_variant: WCE_VARIANT_LS starts at 2, every other knob at 0
+
+
 @contextlib.contextmanager
-def _variant(wce, v):
+def _variant(wce, v, knobs=None):
+    """WCE_VARIANT_R1 = v, and every further knob of `knobs` (which -> value), for one call"""
     lib = wce.load()
+    knobs = dict(knobs or {})
+    knobs.setdefault(R1, v)
     try:
-        assert lib.wce_debug_set_variant(R1, v) == 0
+        for which, value in knobs.items():
+            assert lib.wce_debug_set_variant(which, value) == 0
         yield
     finally:
-        assert lib.wce_debug_set_variant(R1, 0) == 0
+        for which in knobs:
+            assert lib.wce_debug_set_variant(which, VARIANT_DEFAULT.get(which, 0)) == 0
 
 
-def run_estimate(wce, a, route, sem):
-    """a context of the route from the (scaled) preamble, noise variance and covariance, then one estimate call"""
-    r = ROUTES[route]
+def run_estimate(wce, a, route, sem, mask=None, knobs=None, probe=None):
+    """a context of the route from the (scaled) preamble, noise variance and covariance, then one estimate call.
+    mask: the request (the route's own where None); knobs: further wce_debug_set_variant settings for the call
+    (which -> value); probe(ctx, units): called under the knobs before the launch, to name the kernel; a route
+    may be given as its dict of facts"""
+    r = ROUTES[route] if isinstance(route, str) else route
     B = a["tx"].shape[0]
     mode = {"ref": wce.MMSE_REF, "textbook": wce.MMSE_TEXTBOOK, "cov": None}[r["mode"]]
     if r["mode"] == "cov":
@@ -250,7 +261,8 @@ def run_estimate(wce, a, route, sem):
     f32 = bool(r.get("f32"))
     lsdt = np.complex64 if f32 else np.complex128
     sent = lsdt(SENT)
-    mask = wce.PS_MMSE if r.get("mmse_only") else wce.ALL
+    if mask is None:
+        mask = wce.PS_MMSE if r.get("mmse_only") else wce.ALL
     names = [n for n, bit in zip(EST, (wce.LT_LS, wce.PS_LINEAR, wce.PS_CUBIC, wce.PS_SINC, wce.PS_MMSE)) if mask & bit]
     bufs = {n: _dev(wce, np.full((B, HS), SENT, np.complex128 if n == "ps_mmse" else lsdt)) for n in names}
     deq = _dev(wce, np.full((B, FS), sent, lsdt)) if mask & wce.EQUALIZE else None
@@ -260,7 +272,9 @@ def run_estimate(wce, a, route, sem):
             _dev(wce, a["tx_pre"]), _dev(wce, a["ow2"]) if r.get("noise") else None]
     fr = c.frames(keep[0], keep[1], B, frame_stride=FS, block_stride=BS, rx_pre=keep[2], pre_stride=HS,
                   tx_pre=keep[3], block=0, semantics=wce.SEM_MATLAB if sem == "MATLAB" else wce.SEM_C)
-    with _variant(wce, r.get("variant", 0)):
+    with _variant(wce, r.get("variant", 0), knobs):
+        if probe is not None:
+            probe(c, B * (4 if sem == "MATLAB" else 1))
         c.estimate(fr, o, mask | (wce.FRAME_COV if r.get("fc") else 0), ow2=keep[4])
         wce.synchronize()
     out = {n: _unrows(d.numpy(), N, sent if n != "ps_mmse" else SENT, n) for n, d in bufs.items()}
@@ -473,7 +487,7 @@ def _chan_kw(wce, a, taps=True):
     B = a["sym"].shape[0]
     nt = a["taps"].shape[-1]
     keep = [_dev(wce, _rows(a["taps"], nt + 1)), _dev(wce, a["cfo"]), _dev(wce, a["ow2"]), _dev(wce, a["delay"])]
-    kw = dict(cfo=keep[1], ow2=keep[2], delay=keep[3], seed=a["seed"], first_frame=3)
+    kw = dict(cfo=keep[1], ow2=keep[2], delay=keep[3], seed=a["seed"], first_frame=a.get("first_frame", 3))
     if taps:
         kw.update(taps=keep[0], n_taps=nt, taps_stride=nt + 1)
     return kw, keep
