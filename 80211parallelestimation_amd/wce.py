@@ -34,6 +34,9 @@ LS_ALL = 0xF
 ALL = 0x3F
 OUT_LS_F32 = 1         # wce_outputs.flags: LS family + eq stored as complex float
 FRAME_COV = 1 << 6   # WCE_MMSE_FRAME_COV: PS_MMSE covariance from each frame's own preamble
+# the estimators, by result name and mask bit, in the order of wce_outputs' pointers
+_ESTIMATORS = (("lt_ls", LT_LS), ("ps_linear", PS_LINEAR), ("ps_cubic", PS_CUBIC), ("ps_sinc", PS_SINC),
+               ("ps_mmse", PS_MMSE))
 
 MMSE_REF = 0
 MMSE_TEXTBOOK = 1
@@ -1072,104 +1075,174 @@ class Context:
         "fcs_ok" {source: uint32 [B]}, "psdu_rx" {source: uint8 [B][L]}, "seed_rx" {source: uint8 [B]}, "bits_rx"
         {source: uint8 [B][T]} (the decoded rows), "payload" uint8 [B][L - 4], "seeds" uint8 [B] and, with tracker,
         "tracked_fcs_ok" {source: uint32 [B]}; "bits" is the framed bits."""
-        B, T = int(n_frames), info_bits(modulation, rate)
+        runs, f, ow2, bits, framed, _ = self._link(
+            "link_host", modulation, rate, snr_db, n_frames, sources, taps, cfo, delay, capture_len, threshold,
+            backoff, seed, dd_iterations, scale, stf, stf_threshold, psdu_len, knot_period, tracker)
+        T = bits.shape[1]
+        runs = {s: r[0] for s, r in runs.items()}   # one branch, alone
+        res = {s: last["nbiterr"].numpy() for s, (last, tdec, _) in runs.items()}
+        if tracker is not None:
+            res["tracked"] = {s: tdec["nbiterr"].numpy() for s, (last, tdec, _) in runs.items()}
+        res.update(start=f["start"].numpy(), metric=f["metric"].numpy(), cfo=f["cfo"].numpy(), ow2=ow2[0], bits=bits)
+        if psdu_len is not None:
+            rx = {s: last["_psdu"] for s, (last, tdec, _) in runs.items()}
+            res.update(payload=framed[0], seeds=framed[1], fcs_ok={s: d["fcs_ok"].numpy() for s, d in rx.items()},
+                       psdu_rx={s: d["psdu"].numpy() for s, d in rx.items()},
+                       seed_rx={s: d["seed"].numpy() for s, d in rx.items()},
+                       bits_rx={s: np.unpackbits(last["bits"].numpy(), axis=1, bitorder="little")[:, :T]
+                                for s, (last, tdec, _) in runs.items()})
+            if tracker is not None:
+                res["tracked_fcs_ok"] = {s: tdec["_psdu"]["fcs_ok"].numpy() for s, (last, tdec, _) in runs.items()}
+        if stf:
+            res["metric_stf"] = f["metric_stf"].numpy()
+        return res
+
+    def _link(self, who, modulation, rate, snr_db, n_frames, sources, taps, cfo, delay, capture_len, threshold,
+              backoff, seed, dd_iterations, scale, stf, stf_threshold, psdu_len, knot_period, tracker, n_rx=None,
+              branch_loss_db=None, share_sync=False, weighted=False):
+        """link_host's and link_mrc_host's body (`who` names the caller in a refusal): A branches of B packets,
+        queued and synchronised once.  n_rx None: link_host -- one branch through `taps`, received from the
+        transmitter's own capture, nothing shared, copied or combined.  n_rx A: link_mrc_host -- `taps` holds a
+        set per branch, the captures go into one [A B][L] array, and per source the branches are also combined
+        and the B combined frames go through the same chain.
+        -> (runs {source: [alone] or [alone, combined]}, each what _chain_device returns; _capture_front's dict;
+        ow2 [A][B] as transmitted; bits [B][T] as sent; (payload, seeds) or None; the capture on the device)"""
+        mrc = n_rx is not None
+        A, B, T = int(n_rx) if mrc else 1, int(n_frames), info_bits(modulation, rate)
         if psdu_len is not None and not 4 <= int(psdu_len) <= psdu_max_len(modulation, rate):
             raise ValueError(f"psdu_len must be 4..{psdu_max_len(modulation, rate)} octets")
+        if mrc and not 1 <= A <= COMBINE_MAX_BRANCHES:
+            raise ValueError("n_rx must be 1..8")
         if tracker is not None and dd_iterations:
             raise ValueError("tracker with dd_iterations > 0 (decoder-in-the-loop tracking) is not built")
         if tracker is not None:
-            mu, beta = tracker
+            mu, beta = tracker   # not a pair: refused here, before the device
         if self.tx_pre is None:
-            raise ValueError("link_host needs a context built from a tx preamble")
-        names = {LT_LS: "lt_ls", PS_LINEAR: "ps_linear", PS_CUBIC: "ps_cubic", PS_SINC: "ps_sinc", PS_MMSE: "ps_mmse"}
+            raise ValueError(f"{who} needs a context built from a tx preamble")
+        names = {bit: n for n, bit in _ESTIMATORS}
         sources = tuple(sources)
         if not sources or any(s not in names for s in sources):
             raise ValueError("sources must be estimator bits")
+        loss = np.zeros(A)
+        if mrc:
+            taps = _as_c128(taps)
+            if taps.ndim not in (2, 3, 4) or taps.shape[0] != A or (taps.ndim >= 3 and taps.shape[1] != B):
+                raise ValueError("taps must be [A][n_taps], [A][B][n_taps] or [A][B][K][n_taps] complex")
+            if branch_loss_db is not None:
+                loss = np.asarray(branch_loss_db, np.float64)
+            if loss.shape != (A,):
+                raise ValueError("branch_loss_db must be [A]")
         if stf:
             need = 1520 + (np.shape(taps)[-1] if taps is not None else 1) - 1 + \
                 (int(np.max(delay)) if delay is not None else 0)
             if capture_len < need:
                 raise ValueError(f"capture_len {capture_len} cannot hold a packet with a short field: {need} samples")
+        branch = taps if mrc else [taps]
+        N, L = A * B, int(capture_len)
         rng = np.random.default_rng(seed)
         if psdu_len is None:
-            bits = rng.integers(0, 2, (B, T), dtype=np.uint8)
+            bits, framed = rng.integers(0, 2, (B, T), dtype=np.uint8), None
             bits[:, T - 6:] = 0
-            dbits = DeviceArray.from_numpy(np.packbits(bits, axis=1, bitorder="little"))
-            ref, term = bits, True
-        else:
-            dbits, framed = self._psdu_draw(rng, B, 1, modulation, rate, int(psdu_len))
-            ref, term = dbits, False
+            ref = np.tile(bits, (A, 1))
+            dbits = DeviceArray.from_numpy(np.packbits(ref, axis=1, bitorder="little"))
+        else:   # the references stay on the device: the first B rows of dbits are the packets themselves
+            dbits, framed = self._psdu_draw(rng, B, A, modulation, rate, int(psdu_len))
+            ref = bits = dbits
         ow2 = np.ascontiguousarray(np.broadcast_to(
-            (52.0 * scale * scale / 4096.0) / 10.0 ** (np.asarray(snr_db, np.float64) / 10.0), (B,)))
-        dtx = DeviceArray((B, NBLK, NSC), zero=True)
+            (52.0 * scale * scale / 4096.0) / 10.0 ** (np.asarray(snr_db, np.float64) / 10.0), (B,))[None] *
+            10.0 ** (loss / 10.0)[:, None])
+        dtx = DeviceArray((N, NBLK, NSC), zero=True)   # the same symbols once per branch: frame a B + f is packet f
         dpre = DeviceArray.from_numpy(self.tx_pre)
         dfield = DeviceArray((160,), zero=True)   # the clean field: its samples 32..95 are one period, sync's ltf
-        self.reencode(dbits, B, modulation, rate, scale, tx=dtx)
+        self.reencode(dbits, N, modulation, rate, scale, tx=dtx)
         self.modulate(None, 1, dfield, 0, dpre)
-        dcap, keep = self._transmit_device(dtx, B, NBLK, dpre, 0, taps, cfo, ow2, delay, int(capture_len), seed, 0,
-                                           True, knot_period if np.ndim(taps) == 3 else None, stf)
-        dstart, dmetric = DeviceArray((B,), np.int32, zero=True), DeviceArray((B,), np.float64, zero=True)
-        dow2e, dcfo = DeviceArray((B,), np.float64, zero=True), DeviceArray((B,), np.float64, zero=True)
-        drx, drxpre = DeviceArray((B, NBLK, NSC), zero=True), DeviceArray((B, NSC), zero=True)
-        if stf:
-            dmstf = DeviceArray((B,), np.float64, zero=True)
-            self.front_end_sync_stf(dcap, B, capture_len, dfield.addr + 32 * 16, stf_threshold, threshold, backoff,
-                                    dstart, dcfo, dmstf, dmetric)
-            self.front_end_preamble(dcap, B, capture_len, drxpre, dow2e, cfo=dcfo, estimate_cfo=False, start=dstart)
-        else:
-            self.front_end_sync(dcap, B, capture_len, dfield.addr + 32 * 16, threshold, backoff, dstart, dmetric)
-            self.front_end_preamble(dcap, B, capture_len, drxpre, dow2e, cfo=dcfo, start=dstart)
-        self.front_end_blocks(dcap, B, NBLK, drx, cfo=dcfo, start=dstart, capture_len=capture_len)
+        sent = [self._transmit_device(dtx, B, NBLK, dpre, 0, branch[a], cfo, ow2[a], delay, L, seed, a * B, True,
+                                      knot_period if np.ndim(branch[a]) == 3 else None, stf) for a in range(A)]
+        if mrc:
+            dcap, dow2 = DeviceArray((N, L), zero=True), DeviceArray.from_numpy(ow2)
+            for a, (cap_a, _) in enumerate(sent):
+                _check(_lib.wce_memcpy_dtod(c_void_p(dcap.addr + a * B * L * 16), cap_a.ptr, B * L * 16, None),
+                       "wce_memcpy_dtod")
+        else:   # the transmitter's own capture, and its ow2 on the device
+            dcap, dow2 = sent[0][0], sent[0][1][2]
+        f = self._capture_front(dcap, N, L, dfield.addr + 32 * 16, threshold, backoff, stf, stf_threshold,
+                                share=(B, A) if share_sync and A > 1 else None)
         mask = LT_LS
         for s in sources:
             mask |= s
-        outs = {n: DeviceArray((B, NSC), zero=True) for bit, n in names.items() if mask & bit}
-        o = Outputs(*[(outs[n].addr if n in outs else None) for n in names.values()], None, NSC, NBLK * NSC, NSC,
+        outs = {n: DeviceArray((N, NSC), zero=True) for n, bit in _ESTIMATORS if mask & bit}
+        o = Outputs(*[(outs[n].addr if n in outs else None) for n, _ in _ESTIMATORS], None, NSC, NBLK * NSC, NSC,
                     PS_LINEAR, 0)
-        fr = self.frames(dtx, drx, B, rx_pre=drxpre, tx_pre=dpre)
+        fr = self.frames(dtx, f["rx"], N, rx_pre=f["rx_pre"], tx_pre=dpre)
         if mask & PS_MMSE and self.mode == MMSE_TEXTBOOK:
-            self.estimate(fr, o, mask | FRAME_COV, ow2=keep[2])
+            self.estimate(fr, o, mask | FRAME_COV, ow2=dow2)
         else:
             self.estimate(fr, o, mask)
-        runs = {}
+        chain = (modulation, rate, scale, psdu_len is None, int(dd_iterations), tracker, psdu_len)
+        runs, keep = {}, []
         for s in sources:
             h = outs[names[s]]
-            hlt = None if s == LT_LS else outs["lt_ls"]
-            dem = self._demod_device(fr, B, h, hlt, modulation, scale, True, True)
-            dec = self._decode_device(dem["eq"], h, hlt, B, modulation, rate, scale, term, ref)
-            dd = self._dd_device(fr, B, dec["bits"], dem["theta"], modulation, rate, scale, term, dec["_ref"],
-                                 int(dd_iterations)) if dd_iterations else None
-            runs[s] = (dem, dec, dd)
-        tracked = {}
-        if tracker is not None:
-            for s in sources:
-                trk = self._track_device(fr, B, outs[names[s]], mu, beta, modulation, scale, True, True)
-                tracked[s] = (trk, self._decode_device(trk["eq"], None, None, B, modulation, rate, scale, term, ref,
-                                                       h_blocks=trk["h_blocks"]))
-        if psdu_len is not None:
-            rx = {s: self._psdu_device((dd if dd is not None else dec)["bits"], B, modulation, rate, int(psdu_len))
-                  for s, (dem, dec, dd) in runs.items()}
-            trx = {s: self._psdu_device(dec["bits"], B, modulation, rate, int(psdu_len))
-                   for s, (trk, dec) in tracked.items()}
+            runs[s] = [self._chain_device(fr, N, h, None if s == LT_LS else outs["lt_ls"], ref, *chain)]
+            if mrc:
+                drxc, dhc = DeviceArray((B, NBLK, NSC), zero=True), DeviceArray((B, NSC), zero=True)
+                self.combine(f["rx"], h, B, A, f["ow2"] if weighted else None, drxc, dhc)
+                runs[s].append(self._chain_device(self.frames(dtx, drxc, B), B, dhc, None, bits, *chain))
+                keep += [drxc, dhc]
         synchronize()
-        res = {s: (dd if dd is not None else dec)["nbiterr"].numpy() for s, (dem, dec, dd) in runs.items()}
-        if tracker is not None:
-            res["tracked"] = {s: dec["nbiterr"].numpy() for s, (trk, dec) in tracked.items()}
-        res.update(start=dstart.numpy(), metric=dmetric.numpy(), cfo=dcfo.numpy(), ow2=ow2)
-        if psdu_len is None:
-            res["bits"] = bits
-        else:
-            res.update(bits=np.unpackbits(dbits.numpy(), axis=1, bitorder="little")[:, :T], payload=framed[0],
-                       seeds=framed[1], fcs_ok={s: d["fcs_ok"].numpy() for s, d in rx.items()},
-                       psdu_rx={s: d["psdu"].numpy() for s, d in rx.items()},
-                       seed_rx={s: d["seed"].numpy() for s, d in rx.items()},
-                       bits_rx={s: np.unpackbits((dd if dd is not None else dec)["bits"].numpy(), axis=1,
-                                                 bitorder="little")[:, :T] for s, (dem, dec, dd) in runs.items()})
-            if tracker is not None:
-                res["tracked_fcs_ok"] = {s: d["fcs_ok"].numpy() for s, d in trx.items()}
+        if psdu_len is not None:
+            bits = np.unpackbits(dbits.rows(0, B), axis=1, bitorder="little")[:, :T]
+        return runs, f, ow2, bits, framed, dcap
+
+    def _capture_front(self, dcap, N, L, ltf, threshold, backoff, stf, stf_threshold, cfo=True, sample_offset=0,
+                       share=None):
+        """queue the front end on the device capture windows dcap [N][L], each call reading what the one before
+        wrote: front_end_sync against ltf (front_end_sync_stf with stf, which also gives the offset), the field
+        and the blocks at its start.  cfo False (and no stf): no offset is estimated or removed.  share (B, A):
+        the windows are A branches of B packets and sync_share gives every branch the best one's start and
+        offset -- without stf the start first, then the fields for the offsets, then the offset, and the fields
+        again with it.  -> name -> DeviceArray (read them after a synchronize): start, metric, cfo (None without
+        one), ow2 (the estimate), rx, rx_pre and, with stf, metric_stf"""
+        f = {"start": DeviceArray((N,), np.int32, zero=True), "metric": DeviceArray((N,), np.float64, zero=True),
+             "ow2": DeviceArray((N,), np.float64, zero=True),
+             "cfo": DeviceArray((N,), np.float64, zero=True) if cfo or stf else None,
+             "rx": DeviceArray((N, NBLK, NSC), zero=True), "rx_pre": DeviceArray((N, NSC), zero=True)}
+        at = dict(cfo=f["cfo"], start=f["start"])
         if stf:
-            res["metric_stf"] = dmstf.numpy()
-        return res
+            f["metric_stf"] = DeviceArray((N,), np.float64, zero=True)
+            self.front_end_sync_stf(dcap, N, L, ltf, stf_threshold, threshold, backoff, f["start"], f["cfo"],
+                                    f["metric_stf"], f["metric"])
+            if share:
+                self.sync_share(f["metric"], *share, f["start"], f["cfo"])
+        else:
+            self.front_end_sync(dcap, N, L, ltf, threshold, backoff, f["start"], f["metric"])
+            if share:   # one oscillator: the best branch's offset for all, and the fields again with it
+                self.sync_share(f["metric"], *share, f["start"], None)
+                self.front_end_preamble(dcap, N, L, f["rx_pre"], f["ow2"], **at)
+                self.sync_share(f["metric"], *share, None, f["cfo"])
+        self.front_end_preamble(dcap, N, L, f["rx_pre"], f["ow2"], estimate_cfo=not (stf or share), **at)
+        self.front_end_blocks(dcap, N, NBLK, f["rx"], sample_offset=sample_offset, capture_len=L, **at)
+        return f
+
+    def _chain_device(self, frames, n, h, hlt, ref, modulation, rate, scale, terminated, dd_rounds, tracker, psdu_len):
+        """queue one source's receive chain on n frames: demodulate (tracked, against tx) with h and h_lt,
+        soft_demap and viterbi_decode against ref, then dd_rounds decision-directed rounds; with tracker (mu,
+        beta), beside it, track_demodulate from h, soft_demap_blocks and viterbi_decode; with psdu_len,
+        psdu_deframe behind each last decoder, its dict under "_psdu".  -> (the static chain's last decode, the
+        tracked one or None, what else the queued calls read), name -> DeviceArray (read after a synchronize)"""
+        dem = self._demod_device(frames, n, h, hlt, modulation, scale, True, True)
+        dec = self._decode_device(dem["eq"], h, hlt, n, modulation, rate, scale, terminated, ref)
+        last = self._dd_device(frames, n, dec["bits"], dem["theta"], modulation, rate, scale, terminated, dec["_ref"],
+                               dd_rounds) if dd_rounds else dec
+        trk = tdec = None
+        if tracker is not None:
+            trk = self._track_device(frames, n, h, tracker[0], tracker[1], modulation, scale, True, True)
+            tdec = self._decode_device(trk["eq"], None, None, n, modulation, rate, scale, terminated, ref,
+                                       h_blocks=trk["h_blocks"])
+        if psdu_len is not None:
+            last = dict(last, _psdu=self._psdu_device(last["bits"], n, modulation, rate, int(psdu_len)))
+            if tdec is not None:
+                tdec = dict(tdec, _psdu=self._psdu_device(tdec["bits"], n, modulation, rate, int(psdu_len)))
+        return last, tdec, (dem, dec, trk)
 
     def _psdu_draw(self, rng, B, copies, modulation, rate, L):
         """link_host's packets with PSDUs: payload octets [B][L - 4] and scrambler seeds [B] from rng, framed on
@@ -1265,137 +1338,29 @@ class Context:
         unterminated and psdu_deframe follows each chain's last decoder.  The result gains "fcs_ok" {source:
         {"combined": uint32 [B], "branch": uint32 [A][B]}}, "psdu_rx" {source: uint8 [B][L]} (the combined
         chain's), "payload", "seeds" and, with tracker, "tracked_fcs_ok" like "fcs_ok"."""
-        A, B, T = int(n_rx), int(n_frames), info_bits(modulation, rate)
-        if psdu_len is not None and not 4 <= int(psdu_len) <= psdu_max_len(modulation, rate):
-            raise ValueError(f"psdu_len must be 4..{psdu_max_len(modulation, rate)} octets")
-        if not 1 <= A <= COMBINE_MAX_BRANCHES:
-            raise ValueError("n_rx must be 1..8")
-        if tracker is not None and dd_iterations:
-            raise ValueError("tracker with dd_iterations > 0 (decoder-in-the-loop tracking) is not built")
-        if tracker is not None:
-            mu, beta = tracker
-        if self.tx_pre is None:
-            raise ValueError("link_mrc_host needs a context built from a tx preamble")
-        names = {LT_LS: "lt_ls", PS_LINEAR: "ps_linear", PS_CUBIC: "ps_cubic", PS_SINC: "ps_sinc", PS_MMSE: "ps_mmse"}
-        sources = tuple(sources)
-        if not sources or any(s not in names for s in sources):
-            raise ValueError("sources must be estimator bits")
-        taps = _as_c128(taps)
-        if taps.ndim not in (2, 3, 4) or taps.shape[0] != A or (taps.ndim >= 3 and taps.shape[1] != B):
-            raise ValueError("taps must be [A][n_taps], [A][B][n_taps] or [A][B][K][n_taps] complex")
-        loss = np.zeros(A) if branch_loss_db is None else np.asarray(branch_loss_db, np.float64)
-        if loss.shape != (A,):
-            raise ValueError("branch_loss_db must be [A]")
-        if stf:
-            need = 1520 + taps.shape[-1] - 1 + (int(np.max(delay)) if delay is not None else 0)
-            if capture_len < need:
-                raise ValueError(f"capture_len {capture_len} cannot hold a packet with a short field: {need} samples")
-        N, L = A * B, int(capture_len)
-        rng = np.random.default_rng(seed)
-        if psdu_len is None:
-            bits = rng.integers(0, 2, (B, T), dtype=np.uint8)
-            bits[:, T - 6:] = 0
-            all_bits = np.tile(bits, (A, 1))
-            dbits = DeviceArray.from_numpy(np.packbits(all_bits, axis=1, bitorder="little"))
-            term = True
-        else:   # the references stay on the device: the first B rows of dbits are the packets themselves
-            dbits, framed = self._psdu_draw(rng, B, A, modulation, rate, int(psdu_len))
-            all_bits = bits = dbits
-            term = False
-        ow2 = np.ascontiguousarray(np.broadcast_to(
-            (52.0 * scale * scale / 4096.0) / 10.0 ** (np.asarray(snr_db, np.float64) / 10.0), (B,))[None] *
-            10.0 ** (loss / 10.0)[:, None])
-        dtx = DeviceArray((N, NBLK, NSC), zero=True)   # the same symbols once per branch: frame a B + f is packet f
-        dpre = DeviceArray.from_numpy(self.tx_pre)
-        dfield = DeviceArray((160,), zero=True)
-        self.reencode(dbits, N, modulation, rate, scale, tx=dtx)
-        self.modulate(None, 1, dfield, 0, dpre)
-        dcap = DeviceArray((N, L), zero=True)
-        keep = []
-        for a in range(A):
-            cap_a, k = self._transmit_device(dtx, B, NBLK, dpre, 0, taps[a], cfo, ow2[a], delay, L, seed, a * B, True,
-                                             knot_period if taps.ndim == 4 else None, stf)
-            _check(_lib.wce_memcpy_dtod(c_void_p(dcap.addr + a * B * L * 16), cap_a.ptr, B * L * 16, None),
-                   "wce_memcpy_dtod")
-            keep += [cap_a, k]
-        dow2 = DeviceArray.from_numpy(ow2)
-        dstart, dmetric = DeviceArray((N,), np.int32, zero=True), DeviceArray((N,), np.float64, zero=True)
-        dow2e, dcfo = DeviceArray((N,), np.float64, zero=True), DeviceArray((N,), np.float64, zero=True)
-        drx, drxpre = DeviceArray((N, NBLK, NSC), zero=True), DeviceArray((N, NSC), zero=True)
-        share = share_sync and A > 1
-        if stf:
-            dmstf = DeviceArray((N,), np.float64, zero=True)
-            self.front_end_sync_stf(dcap, N, L, dfield.addr + 32 * 16, stf_threshold, threshold, backoff, dstart, dcfo,
-                                    dmstf, dmetric)
-            if share:
-                self.sync_share(dmetric, B, A, dstart, dcfo)
-            self.front_end_preamble(dcap, N, L, drxpre, dow2e, cfo=dcfo, estimate_cfo=False, start=dstart)
-        else:
-            self.front_end_sync(dcap, N, L, dfield.addr + 32 * 16, threshold, backoff, dstart, dmetric)
-            if share:
-                self.sync_share(dmetric, B, A, dstart, None)
-            self.front_end_preamble(dcap, N, L, drxpre, dow2e, cfo=dcfo, start=dstart)
-            if share:   # one oscillator: the best branch's offset for all, and the fields again with it
-                self.sync_share(dmetric, B, A, None, dcfo)
-                self.front_end_preamble(dcap, N, L, drxpre, dow2e, cfo=dcfo, estimate_cfo=False, start=dstart)
-        self.front_end_blocks(dcap, N, NBLK, drx, cfo=dcfo, start=dstart, capture_len=L)
-        mask = LT_LS
-        for s in sources:
-            mask |= s
-        outs = {n: DeviceArray((N, NSC), zero=True) for bit, n in names.items() if mask & bit}
-        o = Outputs(*[(outs[n].addr if n in outs else None) for n in names.values()], None, NSC, NBLK * NSC, NSC,
-                    PS_LINEAR, 0)
-        fr = self.frames(dtx, drx, N, rx_pre=drxpre, tx_pre=dpre)
-        if mask & PS_MMSE and self.mode == MMSE_TEXTBOOK:
-            self.estimate(fr, o, mask | FRAME_COV, ow2=dow2)
-        else:
-            self.estimate(fr, o, mask)
+        runs, f, ow2, bits, framed, dcap = self._link(
+            "link_mrc_host", modulation, rate, snr_db, n_frames, sources, taps, cfo, delay, capture_len, threshold,
+            backoff, seed, dd_iterations, scale, stf, stf_threshold, psdu_len, knot_period, tracker, n_rx,
+            branch_loss_db, share_sync, weighted)
+        A, B = ow2.shape
 
-        def chains(frames, n, h, hlt, ref):   # link_host's runs on n frames -> (static or dd decode, tracked decode)
-            dem = self._demod_device(frames, n, h, hlt, modulation, scale, True, True)
-            dec = self._decode_device(dem["eq"], h, hlt, n, modulation, rate, scale, term, ref)
-            dd = self._dd_device(frames, n, dec["bits"], dem["theta"], modulation, rate, scale, term, dec["_ref"],
-                                 int(dd_iterations)) if dd_iterations else None
-            trk = tdec = None
-            if tracker is not None:
-                trk = self._track_device(frames, n, h, mu, beta, modulation, scale, True, True)
-                tdec = self._decode_device(trk["eq"], None, None, n, modulation, rate, scale, term, ref,
-                                           h_blocks=trk["h_blocks"])
-            last = dd if dd is not None else dec
-            if psdu_len is not None:
-                last = dict(last, _psdu=self._psdu_device(last["bits"], n, modulation, rate, int(psdu_len)))
-                if tdec is not None:
-                    tdec["_psdu"] = self._psdu_device(tdec["bits"], n, modulation, rate, int(psdu_len))
-            return last, tdec, (dem, dec, dd, trk)
-        runs = {}
-        for s in sources:
-            h = outs[names[s]]
-            alone = chains(fr, N, h, None if s == LT_LS else outs["lt_ls"], all_bits)
-            drxc, dhc = DeviceArray((B, NBLK, NSC), zero=True), DeviceArray((B, NSC), zero=True)
-            self.combine(drx, h, B, A, dow2e if weighted else None, drxc, dhc)
-            runs[s] = (alone, chains(self.frames(dtx, drxc, B), B, dhc, None, bits), drxc, dhc)
-        synchronize()
-        res = {s: {"combined": comb[0]["nbiterr"].numpy(), "branch": alone[0]["nbiterr"].numpy().reshape(A, B)}
-               for s, (alone, comb, _, _) in runs.items()}
+        def both(i, get):   # chain i (0: static or decision-directed, 1: tracked) of every source, combined and alone
+            return {s: {"combined": get(comb[i]).numpy(), "branch": get(alone[i]).numpy().reshape(A, B)}
+                    for s, (alone, comb) in runs.items()}
+        res = both(0, lambda d: d["nbiterr"])
         if tracker is not None:
-            res["tracked"] = {s: {"combined": comb[1]["nbiterr"].numpy(),
-                                  "branch": alone[1]["nbiterr"].numpy().reshape(A, B)}
-                              for s, (alone, comb, _, _) in runs.items()}
+            res["tracked"] = both(1, lambda d: d["nbiterr"])
         if psdu_len is not None:
-            flags = lambda i: {s: {"combined": comb[i]["_psdu"]["fcs_ok"].numpy(),
-                                   "branch": alone[i]["_psdu"]["fcs_ok"].numpy().reshape(A, B)}
-                               for s, (alone, comb, _, _) in runs.items()}
-            res.update(fcs_ok=flags(0), payload=framed[0], seeds=framed[1],
-                       psdu_rx={s: comb[0]["_psdu"]["psdu"].numpy() for s, (alone, comb, _, _) in runs.items()})
+            res.update(fcs_ok=both(0, lambda d: d["_psdu"]["fcs_ok"]), payload=framed[0], seeds=framed[1],
+                       psdu_rx={s: comb[0]["_psdu"]["psdu"].numpy() for s, (alone, comb) in runs.items()})
             if tracker is not None:
-                res["tracked_fcs_ok"] = flags(1)
-            bits = np.unpackbits(dbits.rows(0, B), axis=1, bitorder="little")[:, :T]
-        res.update(start=dstart.numpy().reshape(A, B), metric=dmetric.numpy().reshape(A, B),
-                   cfo=dcfo.numpy().reshape(A, B), ow2=ow2, ow2_est=dow2e.numpy().reshape(A, B), bits=bits)
+                res["tracked_fcs_ok"] = both(1, lambda d: d["_psdu"]["fcs_ok"])
+        res.update({n: f[n].numpy().reshape(A, B) for n in ("start", "metric", "cfo")}, ow2=ow2,
+                   ow2_est=f["ow2"].numpy().reshape(A, B), bits=bits)
         if stf:
-            res["metric_stf"] = dmstf.numpy().reshape(A, B)
+            res["metric_stf"] = f["metric_stf"].numpy().reshape(A, B)
         if keep_capture:
-            res["capture"] = dcap.numpy().reshape(A, B, L)
+            res["capture"] = dcap.numpy().reshape(A, B, -1)
         return res
 
     def _dd_device(self, fr, B, dbits, dtheta, modulation, rate, scale, terminated, dref, rounds):
@@ -1649,20 +1614,18 @@ class Context:
         block phases; the dict gains "h_dd" and "decode_dd".  tracker (needs demod): (mu, beta): track_demodulate takes
         demodulate's place with h = the source's output and no h_lt, and soft_demap_blocks soft_demap's; "demod"
         gains h_blocks and h_last."""
-        names = [("lt_ls", LT_LS), ("ps_linear", PS_LINEAR), ("ps_cubic", PS_CUBIC), ("ps_sinc", PS_SINC),
-                 ("ps_mmse", PS_MMSE)]
         lsdt = np.complex64 if ls_f32 else np.complex128
         outs = {n: DeviceArray((B, NSC), np.complex128 if n == "ps_mmse" else lsdt, zero=True)
-                for n, bit in names if mask & bit}
+                for n, bit in _ESTIMATORS if mask & bit}
         deq = DeviceArray((B, NBLK, NSC), lsdt, zero=True) if mask & EQUALIZE else None
-        o = Outputs(*[(outs[n].addr if n in outs else None) for n, _ in names],
+        o = Outputs(*[(outs[n].addr if n in outs else None) for n, _ in _ESTIMATORS],
                     deq.addr if deq is not None else None, NSC, NBLK * NSC, NSC, eq_source,
                     OUT_LS_F32 if ls_f32 else 0)
         fr = self.frames(dtx, drx, B, rx_pre=dpre, block=block, semantics=semantics, tx_pre=dtp)
         self.estimate(fr, o, mask, ow2=dow2)
         dem = dec = dd = None
         if demod is not None:   # same (null) stream: it reads the estimate's outputs in order, no host hop
-            src = {bit: n for n, bit in names}[demod[0]]
+            src = {bit: n for n, bit in _ESTIMATORS}[demod[0]]
             if tracker is not None:
                 dem = self._track_device(fr, B, outs[src], tracker[0], tracker[1], demod[1], demod[2], demod[3], True)
             else:
@@ -1827,31 +1790,16 @@ class Context:
             raise ValueError("tx_lptot must be [B][>= 128] complex")
         dpk, dlp, dcap = DeviceArray.from_numpy(pk), DeviceArray.from_numpy(lp), DeviceArray.from_numpy(cap)
         dltf = DeviceArray.from_numpy(np.ascontiguousarray(lp[0, -FFT_SIZE:]))
-        dstart, dmetric = DeviceArray((B,), np.int32, zero=True), DeviceArray((B,), np.float64, zero=True)
-        dow2 = DeviceArray((B,), np.float64, zero=True)
-        dcfo = DeviceArray((B,), np.float64, zero=True) if (cfo or stf) else None
-        sym = [DeviceArray((B, NBLK, NSC), zero=True) for _ in (0, 1)]
-        pre = [DeviceArray((B, NSC), zero=True) for _ in (0, 1)]
-        self.front_end_blocks(dpk, B, NBLK, sym[0], packet_stride=pk.shape[1])
-        self.front_end_preamble(dlp, B, lp.shape[1], pre[0], None)
+        sym, pre = DeviceArray((B, NBLK, NSC), zero=True), DeviceArray((B, NSC), zero=True)
+        self.front_end_blocks(dpk, B, NBLK, sym, packet_stride=pk.shape[1])
+        self.front_end_preamble(dlp, B, lp.shape[1], pre, None)
         # same (null) stream throughout: each call reads what the one before wrote
-        if stf:
-            dmstf = DeviceArray((B,), np.float64, zero=True)
-            self.front_end_sync_stf(dcap, B, W, dltf, stf_threshold, threshold, backoff, dstart, dcfo, dmstf, dmetric)
-            self.front_end_preamble(dcap, B, W, pre[1], dow2, cfo=dcfo, estimate_cfo=False, start=dstart)
-        else:
-            self.front_end_sync(dcap, B, W, dltf, threshold, backoff, dstart, dmetric)
-            self.front_end_preamble(dcap, B, W, pre[1], dow2, cfo=dcfo, start=dstart)
-        self.front_end_blocks(dcap, B, NBLK, sym[1], cfo=dcfo, sample_offset=sample_offset, start=dstart,
-                              capture_len=W)
-        res = self._estimate_device(sym[0], sym[1], pre[1], B, mask | FRAME_COV, 0, PS_LINEAR, semantics, pre[0],
-                                    False, dow2, dem, dcd)
-        res["ow2"] = dow2.numpy()
-        if cfo or stf:
-            res["cfo"] = dcfo.numpy()
-        res["start"], res["metric"] = dstart.numpy(), dmetric.numpy()
-        if stf:
-            res["metric_stf"] = dmstf.numpy()
+        f = self._capture_front(dcap, B, W, dltf, threshold, backoff, stf, stf_threshold, cfo, sample_offset)
+        res = self._estimate_device(sym, f["rx"], f["rx_pre"], B, mask | FRAME_COV, 0, PS_LINEAR, semantics, pre,
+                                    False, f["ow2"], dem, dcd)
+        for n in ("ow2", "cfo", "start", "metric", "metric_stf"):
+            if f.get(n) is not None:
+                res[n] = f[n].numpy()
         return res
 
 
